@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — training clips/s of the AVM hot path on MI355X (BASELINE.json metric), one JSON line on stdout.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, `config`). Everything else on the line below — roofline and per-kernel figures with
+their counter passes, parity, cpu_baseline, the other precisions, the 40x40 loop, the drop-in path, comm — is measured only
+with --full (the --no-* options then leave parts of it out). --dump-outputs DIR writes what the last timed step returned
+(loss.npy, pred.npy, float32) from rank 0; the inputs are seeded, so two builds run with the same arguments can be compared
+output for output. --full runs the parity probe's forward before the timed steps, which draws one set of dropout masks: its
+outputs are comparable with other --full runs, not with plain ones.
 
 A step = one pass of the hot path over one batch of synthetic input: forward, broadcast-MSE, backward and the
 fused Adam of `AVM` (/root/reference/main.py:187-193) on 64 clips x 16 frames = 1024 frames of 3x224x224 (+ a
@@ -15,9 +23,9 @@ overlapped with backward and averaged inside the fused Adam (cvml_goalnet_amd/dd
 The headline (`value`, `dtype`, `roofline`) is the REFERENCE'S PRECISION: `--dtype f32` (default), every contraction on
 the fp32 matrix cores (`v_mfma_f32_32x32x2_f32`), timed over the full --steps / --warmup. The reduced-precision engine
 (bf16 MFMA contractions, fp32 accumulation / statistics / master weights / Adam; an extension — the reference has no such
-mode) is measured in the same run, with the same K / W, and reported beside it as `bf16_path`.
+mode) is measured with --full in the same run, with the same K / W, and reported beside it as `bf16_path`.
 
-Objects on the JSON line:
+Objects on the JSON line of a --full run:
   roofline      the dominant kernel = the implicit-GEMM convolution forward (conv2 + conv3, 84 % of forward MACs):
                 algorithmic flops of its launches / their duration, measured with HIP events inside the timed steps;
                 peak = 157.3 TFLOP/s (fp32 MFMA) / 2 500 TFLOP/s (dense bf16 MFMA), MI355X_MICROARCH.md. `kernel` is
@@ -342,17 +350,20 @@ def x6_roofline(roof, others, nseg=6.0):
     return roof, others
 
 
-def timed_steps(model, aud, vis, lab, warmup, steps, distributed, dev):
-    """W untimed steps, then exactly K steps bracketed by barrier + synchronize on both sides; max over ranks."""
+def timed_steps(model, aud, vis, lab, warmup, steps, distributed, dev, instrument=True):
+    """W untimed steps, then exactly K steps bracketed by barrier + synchronize on both sides; max over ranks.
+    Returns (seconds, kernel events, loss, pred): loss and pred as the last timed step returned them. Without `instrument`
+    no events are recorded and no extra steps run."""
     import torch.distributed as dist
     for _ in range(warmup):
         model.train_step(aud, vis, lab)
     # inside the timed steps only the forward convolutions are bracketed with events: they run alone on the stream, whereas the
     # backward overlaps weight gradients, the fused Adam and HBM-bound passes on a second stream (avm._Fork) and a bracket there
     # would time the neighbours too. The backward GEMMs are timed afterwards, in two instrumented steps without overlap.
-    model.kernel_events, model.time_labels = {}, {"conv_fwd"}
-    if model.grad_sync is not None:
-        model.grad_sync.timing = {}
+    if instrument:
+        model.kernel_events, model.time_labels = {}, {"conv_fwd"}
+        if model.grad_sync is not None:
+            model.grad_sync.timing = {}
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
@@ -367,6 +378,10 @@ def timed_steps(model, aud, vis, lab, warmup, steps, distributed, dev):
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    loss, pred = loss.clone(), pred.clone()                          # the last timed step's results, whatever later steps reuse
+    assert torch.isfinite(loss).all() and torch.isfinite(pred).all(), "non-finite loss/prediction"
+    if not instrument:
+        return dt, {}, loss, pred
     events = model.kernel_events
     if model.grad_sync is not None:
         model.grad_sync.timing, keep_timing = None, model.grad_sync.timing
@@ -380,8 +395,7 @@ def timed_steps(model, aud, vis, lab, warmup, steps, distributed, dev):
     model.kernel_events = None
     if model.grad_sync is not None:
         model.grad_sync.timing = keep_timing
-    assert torch.isfinite(loss).all() and torch.isfinite(pred).all(), "non-finite loss/prediction"
-    return dt, events, loss
+    return dt, events, loss, pred
 
 
 def reduced_precision_path(dev, dtype, n, h, w, audio, seed, steps, warmup, clips, with_parity):
@@ -397,7 +411,7 @@ def reduced_precision_path(dev, dtype, n, h, w, audio, seed, steps, warmup, clip
         parity = logit_parity(model, h, w, synth.BASE_SEED)
         parity.update({"weights": "random init (before the first optimizer step)", "dropout": "masks from seed formula", "bn": "train"})
         torch.cuda.empty_cache()
-    dt, events, loss = timed_steps(model, aud, vis, lab, warmup, steps, False, dev)
+    dt, events, loss, _ = timed_steps(model, aud, vis, lab, warmup, steps, False, dev)
     roof, others = roofline_of(events, "bf16" if dtype in ("fp16", "bf16x6", "fp16x3") else dtype, n, h, w, clips)
     if dtype in ("bf16x6", "fp16x3"):
         roof, others = x6_roofline(roof, others, 6.0 if dtype == "bf16x6" else 3.0)
@@ -602,6 +616,12 @@ def main():
                     help="f32 (default) = the reference's arithmetic on the fp32 matrix cores; bf16 = bf16-MFMA contractions with "
                          "fp32 accumulation / statistics / master weights (an extension); bf16x6 = the fp32 path with the large "
                          "convolutions on split operands (fp32 values as bf16 triples, six partial products on the 16-bit MFMA: fp32-grade)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline / other_kernels with their counter passes, parity, "
+                         "cpu_baseline, the other precisions, the 40x40 loop, the drop-in path, comm (N > 1); the --no-* options "
+                         "leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss and predictions of the last timed step (rank 0) as DIR/loss.npy, DIR/pred.npy (float32)")
     args = ap.parse_args()
 
     # stdout carries exactly ONE line (the JSON): anything libraries print meanwhile (RCCL prints a version banner to
@@ -613,7 +633,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    if world == 1 and not args.no_live_traffic and os.environ.get("GOALNET_DDP_FORCE") != "1":
+    if args.full and world == 1 and not args.no_live_traffic and os.environ.get("GOALNET_DDP_FORCE") != "1":
         # roofline.traffic of THIS build, from counters: child processes under rocprofv3, started before this process initialises the GPU
         for dt in (("f32", "bf16") if (args.dtype == "f32" and not args.no_second_path) else ((args.dtype,) if args.dtype not in ("bf16x6", "fp16x3") else ())):
             t0 = time.time()
@@ -664,7 +684,7 @@ def main():
 
     single = rank == 0 and world == 1
     parity = None
-    if single and not args.no_cpu_baseline:
+    if single and args.full and not args.no_cpu_baseline:
         try:
             parity = logit_parity(model, h, w, synth.BASE_SEED)     # on the random-init weights, before any optimizer step
             parity.update({"weights": "random init (before the first optimizer step)", "dropout": "masks from seed formula", "bn": "train"})
@@ -676,6 +696,7 @@ def main():
         # forced rank: +80 ms per step over the first steps): get that out of the way before the W warm-up steps
         with torch.no_grad():
             model.forward_device(aud[:2] if aud is not None else None, vis[:2], save=False)      # materialise + sync_params
+    if distributed and args.full:
         probe, bucket_bytes = comm_probe(model, dev, world)
         sharded = model.grad_sync.sharded(model)
         comm = {"ranks": world, "backend": "nccl (RCCL over xGMI)" if backend == "nccl" else "gloo (rehearsal on one GPU: not a measurement)",
@@ -684,7 +705,12 @@ def main():
                          "updated weights (waited for before the next step's linear5); buckets 0, 2: all-reduce" % world) if sharded
                         else "all-reduce of three buckets overlapped with backward, replicated fused Adam",
                 "allreduce_probe_bucket1": probe, "compress": compress}
-    dt, events, loss = timed_steps(model, aud, vis, lab, args.warmup, args.steps, distributed, dev)
+    dt, events, loss, pred = timed_steps(model, aud, vis, lab, args.warmup, args.steps, distributed, dev, instrument=args.full)
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("loss", loss), ("pred", pred)):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), t.detach().float().cpu().numpy())
     if comm is not None and model.grad_sync.timing:
         ev = model.grad_sync.timing.get("exposed_ms", [])
         ex = torch.tensor([sum(a.elapsed_time(b) for a, b in ev) / max(len(ev), 1)], device=dev, dtype=torch.float64)
@@ -708,15 +734,16 @@ def main():
                        ("; linear5.weight gradient exchanged as bf16" if args.compress_bf16 and distributed else ""),
                        "params": int(sum(s.numel for s in model._specs)), "final_loss": float(loss.item())},
         }
-        roof, others = roofline_of(events, "bf16" if args.dtype in ("bf16x6", "fp16x3") else args.dtype, n, h, w, args.clips)
-        if args.dtype in ("bf16x6", "fp16x3"):
-            roof, others = x6_roofline(roof, others, 6.0 if args.dtype == "bf16x6" else 3.0)
-        if roof is not None:
-            res["roofline"] = roof
-            res["other_kernels"] = others
+        if args.full:
+            roof, others = roofline_of(events, "bf16" if args.dtype in ("bf16x6", "fp16x3") else args.dtype, n, h, w, args.clips)
+            if args.dtype in ("bf16x6", "fp16x3"):
+                roof, others = x6_roofline(roof, others, 6.0 if args.dtype == "bf16x6" else 3.0)
+            if roof is not None:
+                res["roofline"] = roof
+                res["other_kernels"] = others
         if comm is not None:
             res["comm"] = comm
-        if single and not args.no_cpu_baseline:
+        if single and args.full and not args.no_cpu_baseline:
             try:
                 if parity is not None:
                     after = logit_parity(model, h, w, synth.BASE_SEED)
@@ -726,7 +753,7 @@ def main():
             except Exception as e:  # the bench line must still be printed
                 log(f"cpu_baseline failed: {e!r}")
                 res["cpu_baseline"] = None
-        if single:
+        if single and args.full:
             del model, aud, vis, lab
             torch.cuda.empty_cache()
             if not args.no_second_path:

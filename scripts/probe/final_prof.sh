@@ -1,6 +1,6 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 20 --warmup 5 > gpurun_out/r03_bench.json 2> gpurun_out/r03_bench.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 > profiles/r03_bench.json; echo "bench rc=$?"
 rm -rf gpurun_out/prof_stats gpurun_out/prof_fetch gpurun_out/prof_write
 BENCH_DTYPE=f32 bash scripts/profile_bench.sh > gpurun_out/r03_prof_f32.log 2>&1; echo "prof f32 rc=$?"
 python scripts/summarize_rocprof.py r03 > gpurun_out/r03_sum_f32.log 2>&1

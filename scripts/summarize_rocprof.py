@@ -35,7 +35,7 @@ if f:
     with open(os.path.join(out, f"{tag}_kernel_stats.md"), "w") as o:
         o.write(f"# rocprofv3 --kernel-trace --stats — bench.py ({tag})\n\n")
         o.write("Command (on the MI355X box, scripts/profile_bench.sh): `rocprofv3 --kernel-trace --stats --output-format csv -- "
-                "python3 bench.py --steps 2 --warmup 2 --no-cpu-baseline --no-native40 --dtype <see bench line>` (4 train steps in the trace: 2 warm-up + 2 timed).\n\n")
+                "python3 bench.py --full --steps 2 --warmup 2 --no-cpu-baseline --no-native40 --no-second-path --no-live-traffic --dtype <see bench line>` (4 train steps in the trace: 2 warm-up + 2 timed).\n\n")
         if bench:
             o.write(f"bench line of the same run: value = {bench['value']:.2f} clips/s, {bench['ms_per_step']:.1f} ms/step; "
                     f"roofline: {json.dumps(bench.get('roofline'))}\n\n")

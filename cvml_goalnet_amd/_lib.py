@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GOALNET_LIB_PATH") or os.path.join(_HERE, "libgoalnet_hip.so")   # override: A/B builds of the kernels
-ABI_VERSION = 4
+ABI_VERSION = 5
 STAT_PARTS = 1024
 
 P = c_void_p  # device pointers and the stream travel as void*
@@ -40,6 +40,8 @@ PROTOTYPES = {
     "goalnet_pool_bnstats_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "goalnet_pool_bnstats_fwd_p16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "goalnet_bn_finalize": (c_int, [P, c_int, P, P, P, P, c_float, c_float, c_int64, c_int, P, P, P, P, P]),
+    "goalnet_pool_bn_eval_fwd": (c_int, [P, c_int, P, c_int, P, P, P, P, P, c_float, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "goalnet_bn_bwd_finalize_eval": (c_int, [P, c_int, P, P, c_int, P, P, P, P]),
     "goalnet_bn_bwd_reduce": (c_int, [P, P, P, P, P, c_int, c_int64, c_int, P]),
     "goalnet_bn_bwd_reduce_t": (c_int, [P, c_int, P, c_int, P, P, P, c_int, c_int64, c_int, c_int, P]),
     "goalnet_bn_bwd_finalize": (c_int, [P, c_int, P, P, P, c_int64, c_int, P, P, P, P]),
@@ -49,6 +51,7 @@ PROTOTYPES = {
     "goalnet_bn_small_ws_bytes": (c_size_t, [c_int]),
     "goalnet_pool_bn_fwd_small": (c_int, [P, P, P, P, P, P, P, c_float, c_float, P, P, P, P, P, c_size_t, P, c_int, c_int, c_int, c_int, P]),
     "goalnet_bn_bwd_reduce_small": (c_int, [P, P, P, P, P, P, P, P, P, c_size_t, P, c_int, c_int, c_int, c_int, P]),
+    "goalnet_bn_bwd_reduce_small_eval": (c_int, [P, P, P, P, P, P, P, P, P, c_size_t, P, c_int, c_int, c_int, c_int, P]),
     "goalnet_bnpool_bwd_small": (c_int, [P, P, P, P, P, P, P, c_size_t, P, c_int, c_int, c_int, c_int, P]),
     "goalnet_partials_sum": (c_int, [P, c_int, c_int64, c_int, P, P]),
     "goalnet_partials_sum2": (c_int, [P, c_int, c_int, P, P, c_int, c_int, P, P]),

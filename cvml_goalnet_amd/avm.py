@@ -9,9 +9,12 @@ Mirrors `/root/reference/utils.py:229-272` (class AVM) and its callers' contract
     torch.save(model.state_dict(), f) / model.load_state_dict(torch.load(f))   # main.py:66, 263, 282
 
 Same sub-module names (`visbl`, `audbl`, `fusion`) and therefore the same `state_dict` keys, shapes and
-torch-native layouts as the reference. The model is always in train mode, as the reference's is (it never
+torch-native layouts as the reference. A fresh model is in train mode, as the reference's is (it never
 calls `.eval()`): BatchNorm uses batch statistics and updates its running buffers on every forward, also
-under `torch.no_grad()`; dropout is live.
+under `torch.no_grad()`; dropout is live. `model.eval()` is honoured as by `nn.BatchNorm2d` / `nn.Dropout`:
+BatchNorm normalises with the running statistics and leaves the buffers (and `num_batches_tracked`) alone,
+the five dropouts are the identity and the dropout counter does not advance; gradients still flow (frozen
+BatchNorm statistics: dp = gamma * invstd_running * dz). `model.train()` restores the train-mode behaviour.
 
 All arithmetic runs in libgoalnet_hip.so (hand-written gfx950 kernels) — there is no CPU or eager-PyTorch
 fallback. Parameters live in ONE flat fp32 arena in device layouts (conv weights OHWI, linear5 columns in
@@ -470,8 +473,8 @@ class AVM(nn.Module):
         self._given_masks = None if masks is None else [m.to(self._device, F32).contiguous() for m in masks]
 
     def _masks(self, n: int):
-        if self.dropout_mode == "off":
-            return [None] * 5
+        if not self.training or self.dropout_mode == "off":
+            return [None] * 5                    # eval(): the five dropouts are the identity and the draw counter stays put
         if self.dropout_mode == "given":
             for m, wdt in zip(self._given_masks, (512, 512, 512, 256, 128)):
                 if tuple(m.shape) != (n, wdt):
@@ -623,6 +626,12 @@ class AVM(nn.Module):
         bn = getattr(self.visbl, f"bnorm{i}")
         st = torch.empty(4, c, dtype=F32, device=dev)
         count = n * (hc - 2) * (wc - 2)
+        if not self.training:
+            # eval(): normalise with the running statistics (a fixed affine known before the pass) -> pool and the four rows of st in
+            # one launch at every shape; the buffers and num_batches_tracked stay as they are, no statistic (and no collective)
+            ops.pool_bn_eval_fwd(y, p, idx, self._pflat(f"visbl.bnorm{i}.weight"), self._pflat(f"visbl.bnorm{i}.bias"),
+                                 bn.running_mean, bn.running_var, BN_EPS, st, n, hc, wc, c)
+            return p, idx, st
         if self._small_bn(y, p, n, hc, wc, c):
             # the reference's operating point (10 frames of 40 x 40): pool, statistics AND the finalise step in one launch
             ops.pool_bn_fwd_small(y, p, idx, self._pflat(f"visbl.bnorm{i}.weight"), self._pflat(f"visbl.bnorm{i}.bias"),
@@ -661,7 +670,7 @@ class AVM(nn.Module):
         dev = self._device
         P = self._pflat
         masks = self._masks(n)
-        ctx = {"n": n, "h": h, "w": w, "bins": bins, "visual": visual, "audio": audio} if save else None
+        ctx = {"n": n, "h": h, "w": w, "bins": bins, "visual": visual, "audio": audio, "eval": not self.training} if save else None
 
         fw = 640 if self.audio_included else 512
         voff = fw - 512
@@ -819,13 +828,15 @@ class AVM(nn.Module):
         p, idx, st = ctx[f"p{i}"], ctx[f"idx{i}"], ctx[f"st{i}"]
         npix = n * (hc - 2) * (wc - 2)
         small = self._small_bn(dbn, p, n, hc, wc, c) and not (self._half and i > 1)
+        frozen = ctx["eval"]          # the forward ran under eval(): st holds the running statistics, constants of the forward
         if small:
             # the reference's operating point: reduce + finalise in one launch (csrc/pool_bn.hip "small shapes"), then the rolling-row
             # max-pool / ReLU backward (13 us; the one-launch 9-window gather from global memory 35), its bias-gradient rows summed at
             # the end of backward on the side stream
             coef3 = torch.empty(3 * c, dtype=F32, device=dev)
-            ops.bn_bwd_reduce_small(dbn, p, st[0], st[1], self._pflat(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.weight"),
-                                    G(f"visbl.bnorm{i}.bias"), coef3, n, hc, wc, c)
+            (ops.bn_bwd_reduce_small_eval if frozen else ops.bn_bwd_reduce_small)(
+                dbn, p, st[0], st[1], self._pflat(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.bias"),
+                coef3, n, hc, wc, c)
             dy = torch.empty(n, hc, wc, c, dtype=F32, device=dev)
             if os.environ.get("GOALNET_SMALL_BNPOOL", "0") == "1":
                 ops.bnpool_bwd_small(dbn, p, idx, coef3, dy, G(f"visbl.conv{i}.bias"), n, hc, wc, c)
@@ -840,9 +851,14 @@ class AVM(nn.Module):
         coef3 = torch.empty(3 * c, dtype=F32, device=dev)
         partials = torch.empty(ops.stat_parts(npix // 64) * 2 * c, dtype=torch.float64, device=dev)
         ops.bn_bwd_reduce(dbn, p, st[0], st[1], partials, npix, c)
-        ops.bn_bwd_finalize(partials, self._pflat(f"visbl.bnorm{i}.weight"), st[0], st[1], npix, c,
-                            G(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.bias"), coef3)
-        if self.stat_sync is not None:
+        if frozen:
+            # dp = gamma invstd dz: no batch means to subtract, hence no cross-rank sums either
+            ops.bn_bwd_finalize_eval(partials, self._pflat(f"visbl.bnorm{i}.weight"), st[1], c,
+                                     G(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.bias"), coef3)
+        else:
+            ops.bn_bwd_finalize(partials, self._pflat(f"visbl.bnorm{i}.weight"), st[0], st[1], npix, c,
+                                G(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.bias"), coef3)
+        if self.stat_sync is not None and not frozen:
             # dgamma / dbeta above are this rank's sums (the gradient all-reduce adds the ranks up); the dx coefficients
             # need the sums over every rank's pixels
             scratch = torch.empty(2 * c, dtype=F32, device=dev)

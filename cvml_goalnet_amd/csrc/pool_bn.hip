@@ -86,12 +86,33 @@ __device__ __forceinline__ double column_sum16(const double* __restrict__ col0, 
     return t;
 }
 
+// Eval mode (model.eval()): BatchNorm is the fixed per-channel affine of the running buffers, known before the pass. The pool
+// kernels below are instantiated with STATS = false for it: no statistic partials; instead the blocks of the first work slot
+// write the four rows st = (mean, invstd, scale, shift) of their channels from gamma, beta and the running buffers (read only).
+struct EvalBN {
+    const float* gamma; const float* beta; const float* rmean; const float* rvar; float eps; float* st;
+};
+__device__ __forceinline__ void bn_eval_coef(int c, int C, const EvalBN& e) {
+    const float m = e.rmean[c];
+    const float is = (float)(1.0 / sqrt((double)e.rvar[c] + (double)e.eps));
+    const float sc = e.gamma[c] * is;
+    e.st[c] = m;
+    e.st[C + c] = is;
+    e.st[2 * C + c] = sc;
+    e.st[3 * C + c] = e.beta[c] - m * sc;                // bn_finalize_one's formulas on the running statistics
+}
+
 // max_pool2d CPU kernel), partial sums of p and p*p per channel.
+template <bool STATS>
 __global__ __launch_bounds__(256) void pool_bnstats_fwd_kernel(const float* __restrict__ y, float* __restrict__ p,
                                                               uint8_t* __restrict__ idx, double* __restrict__ partials,
-                                                              int N, int Hc, int Wc, int C) {
+                                                              int N, int Hc, int Wc, int C, EvalBN ev) {
     __shared__ double smem[256 * 8];
     const int tid = threadIdx.x;
+    if constexpr (!STATS) {
+        if (blockIdx.x == 0)
+            for (int c = tid; c < C; c += 256) bn_eval_coef(c, C, ev);
+    }
     const int G = C >> 2;                 // channel groups of 4; G divides 256
     const int g = tid % G, pl = tid / G;
     const int ppi = 256 / G;              // pixels per block iteration
@@ -121,12 +142,14 @@ __global__ __launch_bounds__(256) void pool_bnstats_fwd_kernel(const float* __re
         *reinterpret_cast<float4*>(p + pix * C + g * 4) = best;
         if (idx) *reinterpret_cast<uint32_t*>(idx + idx_off(pix / ((int64_t)Hp * Wp), pix % ((int64_t)Hp * Wp), g * 4, (int64_t)Hp * Wp, C)) =
                 bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
-        acc[0][0] += (double)best.x; acc[1][0] += (double)best.x * (double)best.x;
-        acc[0][1] += (double)best.y; acc[1][1] += (double)best.y * (double)best.y;
-        acc[0][2] += (double)best.z; acc[1][2] += (double)best.z * (double)best.z;
-        acc[0][3] += (double)best.w; acc[1][3] += (double)best.w * (double)best.w;
+        if constexpr (STATS) {
+            acc[0][0] += (double)best.x; acc[1][0] += (double)best.x * (double)best.x;
+            acc[0][1] += (double)best.y; acc[1][1] += (double)best.y * (double)best.y;
+            acc[0][2] += (double)best.z; acc[1][2] += (double)best.z * (double)best.z;
+            acc[0][3] += (double)best.w; acc[1][3] += (double)best.w * (double)best.w;
+        }
     }
-    block_reduce_store<2>(acc, G, tid, smem, partials + (int64_t)blockIdx.x * 2 * C, C, C);
+    if constexpr (STATS) block_reduce_store<2>(acc, G, tid, smem, partials + (int64_t)blockIdx.x * 2 * C, C, C);
 }
 
 __device__ __forceinline__ void bn_finalize_one(int c, double s, double q, const float* gamma, const float* beta, float* rmean, float* rvar,
@@ -228,6 +251,24 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* __re
     coef3[c] = (float)a;
     coef3[C + c] = (float)b;
     coef3[2 * C + c] = (float)cc;
+}
+
+// eval mode: mean / invstd are the running statistics (constants of the forward), so dp = gamma * invstd * dz; dgamma and dbeta
+// are the same column sums as in train mode
+__global__ __launch_bounds__(256) void bn_bwd_finalize_eval_kernel(const double* __restrict__ partials, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ invstd, int nparts, int C,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                  float* __restrict__ coef3) {
+    __shared__ double sm[256];
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    const double s = column_sum16(partials + c, nparts, 2 * C, c < C, sm);
+    const double q = column_sum16(partials + C + c, nparts, 2 * C, c < C, sm);
+    if (c >= C || threadIdx.x >= 16) return;
+    dbeta[c] = (float)s;
+    dgamma[c] = (float)q;
+    coef3[c] = (float)((double)gamma[c] * (double)invstd[c]);
+    coef3[C + c] = 0.f;
+    coef3[2 * C + c] = 0.f;
 }
 
 // ---- backward phase 3: dy[n,h,w,c] = relu'(y) * sum over the (<= 9) pooling windows that contain (h,w) and
@@ -387,7 +428,9 @@ __global__ __launch_bounds__(SMALL_T) void pool_bn_fwd_small_kernel(const float*
         bn_finalize_one(c, dsm[c], dsm[C + c], gamma, beta, rmean, rvar, momentum, eps, (double)npix, mean, invstd, scale, shift);
 }
 
-// backward, first launch: (sum dz, sum dz xhat) per channel -> dgamma, dbeta and the coefficients of dp = a dz + b p + cc
+// backward, first launch: (sum dz, sum dz xhat) per channel -> dgamma, dbeta and the coefficients of dp = a dz + b p + cc.
+// EVAL: mean / invstd are the running statistics, constants of the forward: dp = gamma invstd dz (b = cc = 0)
+template <bool EVAL = false>
 __global__ __launch_bounds__(SMALL_T) void bn_bwd_reduce_small_kernel(const float* __restrict__ dz, const float* __restrict__ p,
                                                                      const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                      double* __restrict__ partials, int* __restrict__ ctr,
@@ -415,6 +458,12 @@ __global__ __launch_bounds__(SMALL_T) void bn_bwd_reduce_small_kernel(const floa
         dbeta[c] = (float)s;
         dgamma[c] = (float)q;
         const double a = (double)gamma[c] * (double)invstd[c];
+        if constexpr (EVAL) {
+            coef3[c] = (float)a;
+            coef3[C + c] = 0.f;
+            coef3[2 * C + c] = 0.f;
+            continue;
+        }
         const double m1 = s / count, m2 = q / count;
         const double b = -a * m2 * (double)invstd[c];
         coef3[c] = (float)a;
@@ -535,15 +584,18 @@ __device__ __forceinline__ float4 load_p4(const __hip_bfloat16* q) {
 }
 
 // NPW = passes of 32 pixels per conv row (launcher: ceil(Wc / 32) <= 6)
-template <typename YT, typename PT, int NPW>
+template <typename YT, typename PT, int NPW, bool STATS = true>
 __global__ __launch_bounds__(256) void pool_bnstats_fwd_v2_kernel(const YT* __restrict__ y, PT* __restrict__ p,
                                                                  uint8_t* __restrict__ idx, double* __restrict__ partials,
-                                                                 int N, int Hc, int Wc, int C, int bands) {
+                                                                 int N, int Hc, int Wc, int C, int bands, EvalBN ev) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // [3][Wc][CS] floats (>= 16 KB for the reduction)
     const int tid = threadIdx.x, l8 = tid & 7, px = tid >> 3;
     const int ccn = C / CS;
     const int slot = blockIdx.x / ccn, c0 = (blockIdx.x % ccn) * CS + l8 * 4;
     const int Hp = Hc - 2, Wp = Wc - 2;
+    if constexpr (!STATS) {
+        if (slot == 0 && tid < CS) bn_eval_coef((blockIdx.x % ccn) * CS + tid, C, ev);
+    }
     double acc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     // work unit = (frame, band of pooled rows): with few frames (the reference's 10-frame sub-batches) the bands give
     // the grid its parallelism; a unit keeps three conv rows in LDS and rolls down its band
@@ -600,16 +652,20 @@ __global__ __launch_bounds__(256) void pool_bnstats_fwd_v2_kernel(const YT* __re
                 const int64_t o = ((int64_t)ph * Wp + pw) * C;
                 best = store_p4(pn + o, best);
                 if (in) *reinterpret_cast<uint32_t*>(in + ((int64_t)ph * Wp + pw) * CS) = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
-                acc[0][0] += (double)best.x; acc[1][0] += (double)best.x * (double)best.x;
-                acc[0][1] += (double)best.y; acc[1][1] += (double)best.y * (double)best.y;
-                acc[0][2] += (double)best.z; acc[1][2] += (double)best.z * (double)best.z;
-                acc[0][3] += (double)best.w; acc[1][3] += (double)best.w * (double)best.w;
+                if constexpr (STATS) {
+                    acc[0][0] += (double)best.x; acc[1][0] += (double)best.x * (double)best.x;
+                    acc[0][1] += (double)best.y; acc[1][1] += (double)best.y * (double)best.y;
+                    acc[0][2] += (double)best.z; acc[1][2] += (double)best.z * (double)best.z;
+                    acc[0][3] += (double)best.w; acc[1][3] += (double)best.w * (double)best.w;
+                }
             }
             __syncthreads();
         }
     }
-    double* row = partials + (int64_t)slot * 2 * C + (blockIdx.x % ccn) * CS;
-    slice_reduce_store(acc, 2, tid, reinterpret_cast<double*>(smem), row, row + C);
+    if constexpr (STATS) {
+        double* row = partials + (int64_t)slot * 2 * C + (blockIdx.x % ccn) * CS;
+        slice_reduce_store(acc, 2, tid, reinterpret_cast<double*>(smem), row, row + C);
+    }
 }
 
 // ---- 16-bit conv output -> 16-bit pooled activation (the 16-bit modes' blocks 2 and 3): integer keys ----------------------------
@@ -657,10 +713,10 @@ __device__ __attribute__((noinline)) uint2 pool_window_exact(const char* ring, u
 // of loads in flight each. WPL = 32-bit words per lane: 2 (4 channels, 32-channel slices, 64 B per pixel) or 4 (8 channels,
 // 64-channel slices, 128 B per pixel: twice the bytes in flight per thread at about the same occupancy). The pixel -> thread
 // mapping, hence every per-channel summation order, is v2's in both.
-template <bool F16, int NPW, int WPL>
+template <bool F16, int NPW, int WPL, bool STATS = true>
 __global__ __launch_bounds__(256) void pool_bnstats_fwd_k16_kernel(const unsigned short* __restrict__ y, unsigned short* __restrict__ p,
                                                                   uint8_t* __restrict__ idx, double* __restrict__ partials,
-                                                                  int N, int Hc, int Wc, int C, int bands) {
+                                                                  int N, int Hc, int Wc, int C, int bands, EvalBN ev) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // [3][Wc][CSL] 16-bit values; reused by the reduction
     constexpr int CPL = 2 * WPL, CSL = 8 * CPL;                       // channels per lane, per block slice
     typedef unsigned wvec __attribute__((ext_vector_type(WPL)));
@@ -669,6 +725,9 @@ __global__ __launch_bounds__(256) void pool_bnstats_fwd_k16_kernel(const unsigne
     const int ccn = C / CSL;
     const int slot = blockIdx.x / ccn, c0 = (blockIdx.x % ccn) * CSL + l8 * CPL;
     const int Hp = Hc - 2, Wp = Wc - 2;
+    if constexpr (!STATS) {
+        if (slot == 0 && tid < CSL) bn_eval_coef((blockIdx.x % ccn) * CSL + tid, C, ev);
+    }
     constexpr unsigned INF16 = F16 ? 0x7C00u : 0x7F80u;
     constexpr unsigned PIX = CSL * 2;                                 // bytes per pixel in a ring row
     const unsigned rowbytes = (unsigned)Wc * PIX;
@@ -755,11 +814,13 @@ __global__ __launch_bounds__(256) void pool_bnstats_fwd_k16_kernel(const unsigne
                         if (WPL == 2) *reinterpret_cast<uint32_t*>(irow + ioff[ps]) = taps[0] | (taps[1] << 16);
                         else *reinterpret_cast<uint2*>(irow + ioff[ps]) = make_uint2(taps[0] | (taps[1] << 16), taps[WPL - 2] | (taps[WPL - 1] << 16));
                     }
+                    if constexpr (STATS) {
 #pragma unroll
-                    for (int j = 0; j < WPL; ++j) {
-                        const float f0 = h16_to_f32<F16>(pw16[j] & 0xffffu), f1 = h16_to_f32<F16>(pw16[j] >> 16);
-                        acc[0][2 * j] += (double)f0; acc[1][2 * j] += (double)f0 * (double)f0;
-                        acc[0][2 * j + 1] += (double)f1; acc[1][2 * j + 1] += (double)f1 * (double)f1;
+                        for (int j = 0; j < WPL; ++j) {
+                            const float f0 = h16_to_f32<F16>(pw16[j] & 0xffffu), f1 = h16_to_f32<F16>(pw16[j] >> 16);
+                            acc[0][2 * j] += (double)f0; acc[1][2 * j] += (double)f0 * (double)f0;
+                            acc[0][2 * j + 1] += (double)f1; acc[1][2 * j + 1] += (double)f1 * (double)f1;
+                        }
                     }
                 }
             }
@@ -769,6 +830,7 @@ __global__ __launch_bounds__(256) void pool_bnstats_fwd_k16_kernel(const unsigne
             __syncthreads();
         }
     }
+    if constexpr (!STATS) return;
     // per-channel sums over the block in v2's order: lane l8's channels over the pixel lanes px = 0 .. 31
     __syncthreads();
     double* red = reinterpret_cast<double*>(smem);                    // [2][256][CPL]
@@ -978,22 +1040,26 @@ int row_bands(int nparts, int N, int rows) {
     return b < 1 ? 1 : b;
 }
 
-template <typename YT, typename PT>
-static void launch_pool_fwd_v2(int nparts, size_t lds, hipStream_t st, const YT* y, PT* p, uint8_t* idx, double* partials, int N, int Hc, int Wc, int C) {
+template <typename YT, typename PT, bool STATS = true>
+static void launch_pool_fwd_v2(int nparts, size_t lds, hipStream_t st, const YT* y, PT* p, uint8_t* idx, double* partials, int N, int Hc, int Wc, int C,
+                               EvalBN ev = EvalBN{}) {
     const dim3 grid(nparts * (C / CS)), block(256);
     const int bands = row_bands(nparts, N, Hc - 2);
+#define GN_FWD2(NPV) hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, NPV, STATS>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands, ev)
     switch ((Wc + 31) / 32) {                                    // passes of 32 pixels per conv row; the LDS limit keeps Wc <= 170
-    case 1: hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, 1>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands); break;
-    case 2: hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, 2>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands); break;
-    case 3: hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, 3>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands); break;
-    case 4: hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, 4>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands); break;
-    case 5: hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, 5>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands); break;
-    default: hipLaunchKernelGGL((pool_bnstats_fwd_v2_kernel<YT, PT, 6>), grid, block, lds, st, y, p, idx, partials, N, Hc, Wc, C, bands); break;
+    case 1: GN_FWD2(1); break;
+    case 2: GN_FWD2(2); break;
+    case 3: GN_FWD2(3); break;
+    case 4: GN_FWD2(4); break;
+    case 5: GN_FWD2(5); break;
+    default: GN_FWD2(6); break;
     }
+#undef GN_FWD2
 }
 
-template <bool F16, int WPL>
-static void launch_pool_fwd_k16_w(int nparts, hipStream_t st, const void* y, void* p, uint8_t* idx, double* partials, int N, int Hc, int Wc, int C) {
+template <bool F16, int WPL, bool STATS>
+static void launch_pool_fwd_k16_w(int nparts, hipStream_t st, const void* y, void* p, uint8_t* idx, double* partials, int N, int Hc, int Wc, int C,
+                                  EvalBN ev) {
     constexpr int CSL = 16 * WPL;
     const dim3 grid(nparts * (C / CSL)), block(256);
     const int bands = row_bands(nparts, N, Hc - 2);
@@ -1001,22 +1067,25 @@ static void launch_pool_fwd_k16_w(int nparts, hipStream_t st, const void* y, voi
     if (lds < 16384) lds = 16384;                               // the fp64 block reduction reuses the buffer (256 x 8 doubles)
     const unsigned short* yy = (const unsigned short*)y;
     unsigned short* pp = (unsigned short*)p;
+#define GN_FWD16(NPV) hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, NPV, WPL, STATS>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands, ev)
     switch ((Wc + 31) / 32) {
-    case 1: hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, 1, WPL>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands); break;
-    case 2: hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, 2, WPL>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands); break;
-    case 3: hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, 3, WPL>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands); break;
-    case 4: hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, 4, WPL>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands); break;
-    case 5: hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, 5, WPL>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands); break;
-    default: hipLaunchKernelGGL((pool_bnstats_fwd_k16_kernel<F16, 6, WPL>), grid, block, lds, st, yy, pp, idx, partials, N, Hc, Wc, C, bands); break;
+    case 1: GN_FWD16(1); break;
+    case 2: GN_FWD16(2); break;
+    case 3: GN_FWD16(3); break;
+    case 4: GN_FWD16(4); break;
+    case 5: GN_FWD16(5); break;
+    default: GN_FWD16(6); break;
     }
+#undef GN_FWD16
 }
 
-template <bool F16>
-static void launch_pool_fwd_k16(int nparts, hipStream_t st, const void* y, void* p, uint8_t* idx, double* partials, int N, int Hc, int Wc, int C) {
+template <bool F16, bool STATS = true>
+static void launch_pool_fwd_k16(int nparts, hipStream_t st, const void* y, void* p, uint8_t* idx, double* partials, int N, int Hc, int Wc, int C,
+                                EvalBN ev = EvalBN{}) {
     const char* w = getenv("GOALNET_POOL_K16_WPL");             // 2 | 4: A/B runs
     const bool wide = C % 64 == 0 && (size_t)3 * Wc * 64 * 2 <= 64 * 1024 && !(w && w[0] == '2');
-    if (wide) launch_pool_fwd_k16_w<F16, 4>(nparts, st, y, p, idx, partials, N, Hc, Wc, C);
-    else launch_pool_fwd_k16_w<F16, 2>(nparts, st, y, p, idx, partials, N, Hc, Wc, C);
+    if (wide) launch_pool_fwd_k16_w<F16, 4, STATS>(nparts, st, y, p, idx, partials, N, Hc, Wc, C, ev);
+    else launch_pool_fwd_k16_w<F16, 2, STATS>(nparts, st, y, p, idx, partials, N, Hc, Wc, C, ev);
 }
 
 template <typename DZ, typename PT, bool F16 = false>
@@ -1059,7 +1128,7 @@ int goalnet_pool_bnstats_fwd(const float* y, float* p, uint8_t* idx, double* par
         const size_t need = lds < 16384 ? 16384 : lds;      // the fp64 block reduction reuses the buffer (256 x 8 doubles)
         launch_pool_fwd_v2<float, float>(nparts, need, (hipStream_t)stream, y, p, idx, partials, N, Hc, Wc, C);
     } else {
-        hipLaunchKernelGGL(pool_bnstats_fwd_kernel, dim3(nparts), dim3(256), 0, (hipStream_t)stream, y, p, idx, partials, N, Hc, Wc, C);
+        hipLaunchKernelGGL(pool_bnstats_fwd_kernel<true>, dim3(nparts), dim3(256), 0, (hipStream_t)stream, y, p, idx, partials, N, Hc, Wc, C, EvalBN{});
     }
     GN_LAUNCH_CHECK("pool_bnstats_fwd");
     return 0;
@@ -1102,6 +1171,48 @@ int goalnet_bn_finalize(const double* partials, int nparts, const float* gamma, 
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, (hipStream_t)stream, partials, gamma, beta,
                        running_mean, running_var, momentum, eps, (double)count, nparts, C, mean, invstd, scale, shift);
     GN_LAUNCH_CHECK("bn_finalize");
+    return 0;
+}
+
+int goalnet_pool_bn_eval_fwd(const void* y, int y_16, void* p, int p_16, uint8_t* idx, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, float* st, int nparts,
+                             int N, int Hc, int Wc, int C, int f16, void* stream) {
+    GN_REQUIRE(y && p && gamma && beta && running_mean && running_var && st, GOALNET_E_NULL, "pool_bn_eval_fwd: null pointer");
+    GN_PARTS_OK("pool_bn_eval_fwd");
+    GN_REQUIRE(N > 0 && Hc >= 3 && Wc >= 3, GOALNET_E_SHAPE, "pool_bn_eval_fwd: need Hc, Wc >= 3");
+    GN_REQUIRE(chan_ok(C), GOALNET_E_SHAPE, "pool_bn_eval_fwd: C=%d must be 4*2^k, <= 1024", C);
+    GN_REQUIRE(p_16 || !y_16, GOALNET_E_SHAPE, "pool_bn_eval_fwd: a 16-bit y needs a 16-bit p");
+    GN_REQUIRE(aligned16(y) && aligned16(p) && aligned16(st) && (reinterpret_cast<uintptr_t>(idx) & 3u) == 0, GOALNET_E_ALIGN,
+               "pool_bn_eval_fwd: pointers must be 16-byte aligned");
+    const size_t lds = (size_t)3 * Wc * CS * sizeof(float);
+    const bool v2 = C % CS == 0 && lds <= 64 * 1024;
+    GN_REQUIRE(v2 || !p_16, GOALNET_E_SHAPE, "pool_bn_eval_fwd: a 16-bit p needs C %% 32 == 0 and Wc <= 170");
+    const size_t need = lds < 16384 ? 16384 : lds;
+    const EvalBN ev{gamma, beta, running_mean, running_var, eps, st};
+    hipStream_t s = (hipStream_t)stream;
+    typedef __hip_bfloat16 bf;
+    typedef _Float16 hf;
+    if (!p_16) {
+        if (v2) launch_pool_fwd_v2<float, float, false>(nparts, need, s, (const float*)y, (float*)p, idx, nullptr, N, Hc, Wc, C, ev);
+        else hipLaunchKernelGGL(pool_bnstats_fwd_kernel<false>, dim3(nparts), dim3(256), 0, s, (const float*)y, (float*)p, idx, nullptr,
+                                N, Hc, Wc, C, ev);
+    } else if (y_16) {                                             // the integer-key kernel, as goalnet_pool_bnstats_fwd_p16
+        if (f16) launch_pool_fwd_k16<true, false>(nparts, s, y, p, idx, nullptr, N, Hc, Wc, C, ev);
+        else launch_pool_fwd_k16<false, false>(nparts, s, y, p, idx, nullptr, N, Hc, Wc, C, ev);
+    } else if (f16) launch_pool_fwd_v2<float, hf, false>(nparts, need, s, (const float*)y, (hf*)p, idx, nullptr, N, Hc, Wc, C, ev);
+    else launch_pool_fwd_v2<float, bf, false>(nparts, need, s, (const float*)y, (bf*)p, idx, nullptr, N, Hc, Wc, C, ev);
+    GN_LAUNCH_CHECK("pool_bn_eval_fwd");
+    return 0;
+}
+
+int goalnet_bn_bwd_finalize_eval(const double* partials, int nparts, const float* gamma, const float* invstd, int C,
+                                 float* dgamma, float* dbeta, float* coef3, void* stream) {
+    GN_REQUIRE(partials && gamma && invstd && dgamma && dbeta && coef3, GOALNET_E_NULL, "bn_bwd_finalize_eval: null pointer");
+    GN_REQUIRE(C > 0, GOALNET_E_SHAPE, "bn_bwd_finalize_eval: bad dims");
+    GN_PARTS_OK("bn_bwd_finalize_eval");
+    hipLaunchKernelGGL(bn_bwd_finalize_eval_kernel, dim3((C + 15) / 16), dim3(256), 0, (hipStream_t)stream, partials, gamma, invstd,
+                       nparts, C, dgamma, dbeta, coef3);
+    GN_LAUNCH_CHECK("bn_bwd_finalize_eval");
     return 0;
 }
 
@@ -1251,9 +1362,24 @@ int goalnet_bn_bwd_reduce_small(const float* dz, const float* p, const float* me
                GOALNET_E_ALIGN, "bn_bwd_reduce_small: alignment");
     GN_REQUIRE(ws_bytes >= goalnet_bn_small_ws_bytes(C), GOALNET_E_WORKSPACE, "bn_bwd_reduce_small: workspace too small");
     const int npool = N * (Hc - 2) * (Wc - 2);
-    hipLaunchKernelGGL(bn_bwd_reduce_small_kernel, dim3(small_blocks(npool, C)), dim3(SMALL_T), SMALL_T * 4 * sizeof(double), (hipStream_t)stream,
+    hipLaunchKernelGGL(bn_bwd_reduce_small_kernel<false>, dim3(small_blocks(npool, C)), dim3(SMALL_T), SMALL_T * 4 * sizeof(double), (hipStream_t)stream,
                        dz, p, mean, invstd, (double*)ws, ctr, gamma, dgamma, dbeta, coef3, npool, C);
     GN_LAUNCH_CHECK("bn_bwd_reduce_small");
+    return 0;
+}
+
+int goalnet_bn_bwd_reduce_small_eval(const float* dz, const float* p, const float* mean, const float* invstd, const float* gamma,
+                                     float* dgamma, float* dbeta, float* coef3, void* ws, size_t ws_bytes, int* ctr,
+                                     int N, int Hc, int Wc, int C, void* stream) {
+    GN_REQUIRE(dz && p && mean && invstd && gamma && dgamma && dbeta && coef3 && ws && ctr, GOALNET_E_NULL, "bn_bwd_reduce_small_eval: null pointer");
+    GN_REQUIRE(N > 0 && Hc >= 3 && Wc >= 3 && small_ok(N, Hc, Wc, C), GOALNET_E_SHAPE, "bn_bwd_reduce_small_eval: bad dims");
+    GN_REQUIRE(aligned16(dz) && aligned16(p) && aligned16(coef3) && aligned16(mean) && aligned16(invstd) && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0,
+               GOALNET_E_ALIGN, "bn_bwd_reduce_small_eval: alignment");
+    GN_REQUIRE(ws_bytes >= goalnet_bn_small_ws_bytes(C), GOALNET_E_WORKSPACE, "bn_bwd_reduce_small_eval: workspace too small");
+    const int npool = N * (Hc - 2) * (Wc - 2);
+    hipLaunchKernelGGL(bn_bwd_reduce_small_kernel<true>, dim3(small_blocks(npool, C)), dim3(SMALL_T), SMALL_T * 4 * sizeof(double), (hipStream_t)stream,
+                       dz, p, mean, invstd, (double*)ws, ctr, gamma, dgamma, dbeta, coef3, npool, C);
+    GN_LAUNCH_CHECK("bn_bwd_reduce_small_eval");
     return 0;
 }
 

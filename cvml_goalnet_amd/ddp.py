@@ -243,7 +243,10 @@ class SyncStats:
 
     Gradients are then SUMMED, not averaged (`GradSync(average=False)`), which makes a W-rank step equal to one
     reference process stepping on the concatenation of the W shards (tests/test_gpu_ddp.py). Every rank must hold
-    the same number of frames. Six small collectives per step (3 forward, 3 backward) + two all-gathers: latency-bound."""
+    the same number of frames. Six small collectives per step (3 forward, 3 backward) + two all-gathers: latency-bound.
+
+    After `model.eval()` BatchNorm normalises with the running statistics, which every rank already holds: the six BatchNorm
+    collectives are not issued (AVM._bn_block / AVM._block_bwd), and no dropout rows are drawn."""
 
     def __init__(self, process_group=None):
         if not dist.is_initialized():

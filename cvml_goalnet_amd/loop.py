@@ -42,7 +42,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._seen = set()
         self._pool = None
@@ -100,6 +100,8 @@ class VideoTrainer:
         """What an eager train_step does on the host besides launching kernels."""
         m = self.model
         m._adam_t += 1
+        if not m.training:
+            return                                  # eval(): no dropout draw, BatchNorm buffers untouched
         if m.dropout_mode == "device":
             m._drop_step += 1
         for i in (1, 2, 3):
@@ -111,7 +113,9 @@ class VideoTrainer:
             self._sub_step(n)                       # collectives / supplied masks / per-kernel timing: eager
             self.eager_steps += 1
             return
-        gkey = (n, m._loss_scale_for(n))                # the loss scale is a host scalar baked into the captured launches
+        # the loss scale is a host scalar baked into the captured launches; the mode picks other kernels (eval(): running-stat
+        # BatchNorm, no dropout), so a graph captured in one mode is never replayed in the other
+        gkey = (n, m._loss_scale_for(n), m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -147,9 +151,11 @@ class VideoTrainer:
 
     # ---- validation pass ---------------------------------------------------------------------------------------------
     def eval_video(self, val_audios, val_frames, val_labels):
-        """main.py:218-226 for one video: the whole video in ONE forward under no_grad (BatchNorm in train mode, running
-        statistics updated, dropout live — the reference never calls .eval()), then nn.MSELoss with its (n,1) x (n,)
-        broadcast. Returns (loss (1,), predictions (N,)) as GPU tensors; nothing has been synchronised."""
+        """main.py:218-226 for one video: the whole video in ONE forward under no_grad, then nn.MSELoss with its (n,1) x (n,)
+        broadcast. The forward follows the model's mode: in train mode (the reference's, it never calls .eval()) BatchNorm uses
+        batch statistics and updates its running buffers and dropout is live; after model.eval() BatchNorm uses the running
+        statistics, nothing is updated and dropout is off. Returns (loss (1,), predictions (N,)) as GPU tensors; nothing has
+        been synchronised."""
         m = self.model
         m._require_device()
         aud, vis, _ = m._to_device_inputs(val_audios, val_frames)

@@ -227,6 +227,45 @@ def bn_bwd_reduce_small(dz, p, mean, invstd, gamma, dgamma, dbeta, coef3, N, Hc,
           "bn_bwd_reduce_small")
 
 
+def pool_bn_eval_fwd(y, p, idx, gamma, beta, rmean, rvar, eps, st, N, Hc, Wc, C):
+    """eval mode, one launch: max-pool (+ argmax when idx is given) as pool_bnstats_fwd stores it, and st = (4, C) = (running_mean,
+    invstd, scale, shift) from the running buffers (read only). y / p: fp32, or 16-bit as the 16-bit paths store them."""
+    _chk(y, p, idx, gamma, beta, rmean, rvar, st)
+    _req(y.numel() == N * Hc * Wc * C and p.numel() == N * (Hc - 2) * (Wc - 2) * C, "pool_bn_eval_fwd: y (N,Hc,Wc,C) and p (N,Hc-2,Wc-2,C)")
+    _req(idx is None or (idx.dtype == torch.uint8 and idx.numel() == p.numel()), "pool_bn_eval_fwd: idx must be uint8, one per pooled element")
+    _req(p.dtype in H16 or y.dtype == F32, "pool_bn_eval_fwd: a 16-bit y needs a 16-bit p")
+    for t in (gamma, beta, rmean, rvar):
+        _req(t.dtype == F32 and t.numel() == C and t.is_contiguous(), "pool_bn_eval_fwd: gamma, beta, running stats must be fp32 (C)")
+    _req(st.dtype == F32 and st.numel() == 4 * C and st.is_contiguous(), "pool_bn_eval_fwd: st must be fp32 (4, C)")
+    check(lib().goalnet_pool_bn_eval_fwd(y.data_ptr(), int(y.dtype in H16), p.data_ptr(), int(p.dtype in H16), _p(idx), gamma.data_ptr(),
+                                         beta.data_ptr(), rmean.data_ptr(), rvar.data_ptr(), eps, st.data_ptr(), stat_parts(8 * N),
+                                         N, Hc, Wc, C, _f16(y, p), _s()), "pool_bn_eval_fwd")
+    return p, idx, st
+
+
+def bn_bwd_finalize_eval(partials, gamma, invstd, C, dgamma, dbeta, coef3):
+    """eval mode: dgamma, dbeta from bn_bwd_reduce's partials (taken with the running mean / invstd), coef3 = (gamma invstd, 0, 0)"""
+    _chk(partials, gamma, invstd, dgamma, dbeta, coef3)
+    _req(coef3.numel() == 3 * C and dgamma.numel() == C and dbeta.numel() == C and gamma.numel() == C and invstd.numel() == C,
+         "bn_bwd_finalize_eval: gamma, invstd, dgamma, dbeta (C), coef3 (3 C)")
+    check(lib().goalnet_bn_bwd_finalize_eval(partials.data_ptr(), _rows(partials, 2 * C), gamma.data_ptr(), invstd.data_ptr(), C,
+                                             dgamma.data_ptr(), dbeta.data_ptr(), coef3.data_ptr(), _s()), "bn_bwd_finalize_eval")
+
+
+def bn_bwd_reduce_small_eval(dz, p, mean, invstd, gamma, dgamma, dbeta, coef3, N, Hc, Wc, C):
+    """eval-mode bn_bwd_reduce_small: mean / invstd are the running statistics; coef3 = (gamma invstd, 0, 0)"""
+    _chk(dz, p, mean, invstd, gamma, dgamma, dbeta, coef3)
+    npool = N * (Hc - 2) * (Wc - 2) * C
+    _req(dz.dtype == F32 and p.dtype == F32 and dz.numel() == p.numel() == npool, "bn_bwd_reduce_small_eval: fp32 dz / p of the pooled shape")
+    _req(dgamma.numel() == C and dbeta.numel() == C and coef3.numel() == 3 * C, "bn_bwd_reduce_small_eval: dgamma, dbeta (C), coef3 (3 C)")
+    nbytes = lib().goalnet_bn_small_ws_bytes(C)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dz.device)
+    ctr = _tile_counters(("bn_bwd_reduce_eval", N, Hc, Wc, C), dz.device)
+    check(lib().goalnet_bn_bwd_reduce_small_eval(dz.data_ptr(), p.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+                                                 dgamma.data_ptr(), dbeta.data_ptr(), coef3.data_ptr(), ws.data_ptr(), nbytes,
+                                                 ctr.data_ptr(), N, Hc, Wc, C, _s()), "bn_bwd_reduce_small_eval")
+
+
 def bnpool_bwd_small(dz, p, idx, coef3, dy, dbias, N, Hc, Wc, C):
     """bnpool_bwd + the conv bias gradient in one launch (small fp32 shapes; a direct 9-window gather)"""
     _chk(dz, p, idx, coef3, dy, dbias)

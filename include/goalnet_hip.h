@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GOALNET_ABI_VERSION 4
+#define GOALNET_ABI_VERSION 5
 
 #define GOALNET_OK 0
 #define GOALNET_E_NULL (-1)      /* required pointer is NULL */
@@ -87,6 +87,19 @@ int goalnet_pool_bnstats_fwd_p16(const void* y, int y_bf16, void* p_bf16, uint8_
 int goalnet_bn_finalize(const double* partials, int nparts, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, float momentum, float eps, int64_t count,
                         int C, float* mean, float* invstd, float* scale, float* shift, void* stream);
+/* Eval mode (nn.Module.eval()): BatchNorm normalises with the running statistics, a per-channel affine known before the pass.
+ * One launch: p = maxpool3x3s1(y) and idx (nullable) exactly as goalnet_pool_bnstats_fwd / _p16 write them (same kernels without
+ * the statistics), and st[4][C] = (running_mean, invstd = 1/sqrt(running_var + eps), scale = gamma*invstd, shift = beta -
+ * mean*scale), written by the blocks of the first work slot. The running buffers are read, never written; no partials.
+ * y fp32 (y_16 = 0) or 16-bit (1); p fp32 (p_16 = 0) or 16-bit (1, needs C % 32 == 0 and Wc <= 170); f16: the 16-bit format is
+ * IEEE fp16 rather than bf16. nparts sizes the grid as for goalnet_pool_bnstats_fwd. */
+int goalnet_pool_bn_eval_fwd(const void* y, int y_16, void* p, int p_16, uint8_t* idx, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, float* st, int nparts,
+                             int N, int Hc, int Wc, int C, int f16, void* stream);
+/* eval-mode phase 2: from the partials of goalnet_bn_bwd_reduce(_t) called with the running mean and invstd, dgamma =
+ * sum(dz * xhat), dbeta = sum(dz) and coef3 = (gamma * invstd, 0, 0): the statistics are constants, so dp = gamma * invstd * dz. */
+int goalnet_bn_bwd_finalize_eval(const double* partials, int nparts, const float* gamma, const float* invstd, int C,
+                                 float* dgamma, float* dbeta, float* coef3, void* stream);
 /* BatchNorm backward, phase 1: per-channel sum(dz) and sum(dz * xhat) -> partials (double). */
 int goalnet_bn_bwd_reduce(const float* dz, const float* p, const float* mean, const float* invstd,
                           double* partials, int nparts, int64_t npix, int C, void* stream);
@@ -129,6 +142,10 @@ int goalnet_pool_bn_fwd_small(const float* y, float* p, uint8_t* idx, const floa
 int goalnet_bn_bwd_reduce_small(const float* dz, const float* p, const float* mean, const float* invstd, const float* gamma,
                                 float* dgamma, float* dbeta, float* coef3, void* ws, size_t ws_bytes, int* ctr,
                                 int N, int Hc, int Wc, int C, void* stream);
+/* eval-mode goalnet_bn_bwd_reduce_small: mean / invstd are the running statistics; coef3 = (gamma * invstd, 0, 0) */
+int goalnet_bn_bwd_reduce_small_eval(const float* dz, const float* p, const float* mean, const float* invstd, const float* gamma,
+                                     float* dgamma, float* dbeta, float* coef3, void* ws, size_t ws_bytes, int* ctr,
+                                     int N, int Hc, int Wc, int C, void* stream);
 int goalnet_bnpool_bwd_small(const float* dz, const float* p, const uint8_t* idx, const float* coef3, float* dy, float* dbias,
                              void* ws, size_t ws_bytes, int* ctr, int N, int Hc, int Wc, int C, void* stream);
 /* same in double: the one-row form of a partials array that a rank contributes to the cross-rank BatchNorm sums

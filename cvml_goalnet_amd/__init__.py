@@ -2,11 +2,13 @@
 frame-importance model (forward, broadcast-MSE, backward, Adam) behind the reference's own Python
 surface. See DESIGN.md / INTEGRATION.md.
 
-    from cvml_goalnet_amd import AVM          # drop-in for /root/reference/utils.py:229 `AVM`
+    from cvml_goalnet_amd import AVM               # drop-in for /root/reference/utils.py:229 `AVM`
+    from cvml_goalnet_amd import VideoSummarizer   # /root/reference/main.py:315-345 (`--infer`) on a video resident on the GPU
 """
 from . import synth  # noqa: F401
 from ._lib import GoalnetError, LIB_PATH  # noqa: F401
 from .avm import AVM  # noqa: F401
 from . import optim  # noqa: F401
+from .summarize import VideoSummarizer, VideoSummary  # noqa: F401
 
-__all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim"]
+__all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "VideoSummarizer", "VideoSummary"]

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GOALNET_LIB_PATH") or os.path.join(_HERE, "libgoalnet_hip.so")   # override: A/B builds of the kernels
-ABI_VERSION = 5
+ABI_VERSION = 6
 STAT_PARTS = 1024
 
 P = c_void_p  # device pointers and the stream travel as void*
@@ -138,6 +138,9 @@ PROTOTYPES = {
     "goalnet_rows_scatter_tick": (c_int, [ctypes.POINTER(RowCopy), c_int, P, c_int64, c_int64, c_int64, c_int64, P, P]),
     "goalnet_rows_copy_batch": (c_int, [ctypes.POINTER(RowCopy), c_int, P]),
     "goalnet_frames_preprocess": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P]),
+    "goalnet_frames_preprocess_strided": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P]),
+    "goalnet_gather_clips_ws_bytes": (c_size_t, [c_int]),
+    "goalnet_gather_clips": (c_int, [P, c_int, c_int64, P, P, c_int, P, c_int64, P, P, P, P, c_size_t, P]),
     "goalnet_knapsack_ws_bytes": (c_size_t, [c_int, c_int]),
     "goalnet_knapsack": (c_int, [P, P, c_int, c_int, P, P, c_size_t, P]),
     "goalnet_fscore": (c_int, [P, P, c_int, c_int, P, P, P]),

@@ -8,6 +8,7 @@
 // centres fx = (dx + 0.5) * scale - 0.5, floor, clamp to the border, horizontal pass then vertical pass, no antialiasing)
 // and agree with each other bit for bit.
 #include "common.h"
+#include "frame_resize.h"
 
 using namespace goalnet;
 
@@ -30,37 +31,11 @@ __global__ __launch_bounds__(256) void frame_minmax_kernel(const uint8_t* __rest
     }
 }
 
-// rounded product / sum without fma contraction (OpenCV's scalar path multiplies and adds separately)
-__device__ __forceinline__ float mul_rn(float a, float b) { return __builtin_fmaf(a, b, 0.0f); }
-
+// the per-pixel arithmetic lives in frame_resize.h, shared with the strided entry point (summary.hip)
 __global__ __launch_bounds__(256) void frame_resize_kernel(const uint8_t* __restrict__ frames, const int32_t* __restrict__ minmax,
                                                           float* __restrict__ out, int N, int H0, int W0, int H, int W,
                                                           double scale_x, double scale_y) {
-    const int64_t total = (int64_t)N * 3 * H * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int dx = (int)(i % W), dy = (int)((i / W) % H), c = (int)((i / ((int64_t)W * H)) % 3);
-        const int64_t n = i / ((int64_t)3 * H * W);
-        // source coordinates, resize.cpp: fx = (float)((dx + 0.5) * scale_x - 0.5); sx = floor(fx); fx -= sx; border clamp
-        float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= (float)sx;
-        if (sx < 0) { sx = 0; fx = 0.f; }
-        if (sx >= W0 - 1) { sx = W0 - 1; fx = 0.f; }
-        float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
-        int sy = (int)floorf(fy);
-        fy -= (float)sy;
-        if (sy < 0) { sy = 0; fy = 0.f; }
-        if (sy >= H0 - 1) { sy = H0 - 1; fy = 0.f; }
-        const int sx1 = sx + 1 < W0 ? sx + 1 : W0 - 1, sy1 = sy + 1 < H0 ? sy + 1 : H0 - 1;
-        const int mn = minmax[2 * n], mx = minmax[2 * n + 1];
-        const double den = (double)(mx - mn) + 1e-7;                        // uint8 difference, then + 1e-7 in float64
-        const uint8_t* f = frames + n * (int64_t)H0 * W0 * 3;
-        auto px = [&](int yy, int xx) -> float { return (float)((double)(f[((int64_t)yy * W0 + xx) * 3 + c] - mn) / den); };
-        const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
-        const float h0 = mul_rn(px(sy, sx), a0) + mul_rn(px(sy, sx1), a1);   // horizontal pass on the two source rows
-        const float h1 = mul_rn(px(sy1, sx), a0) + mul_rn(px(sy1, sx1), a1);
-        out[i] = mul_rn(h0, b0) + mul_rn(h1, b1);                           // vertical pass
-    }
+    frame_resize_all(frames, (int64_t)H0 * W0 * 3, minmax, out, N, H0, W0, H, W, scale_x, scale_y);
 }
 
 }  // namespace
@@ -74,13 +49,8 @@ int goalnet_frames_preprocess(const uint8_t* frames_hwc, int N, int H0, int W0, 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(frame_minmax_kernel, dim3(N), dim3(256), 0, st, frames_hwc, (int64_t)H0 * W0 * 3, minmax);
     GN_LAUNCH_CHECK("frames_preprocess.minmax");
-    const int64_t total = (int64_t)N * 3 * H * W;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    // cv2.resize: inv_scale = dsize / ssize (double), scale = 1 / inv_scale
-    const double scale_x = 1.0 / ((double)W / (double)W0), scale_y = 1.0 / ((double)H / (double)H0);
-    hipLaunchKernelGGL(frame_resize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, frames_hwc, (const int32_t*)minmax, out_nchw,
-                       N, H0, W0, H, W, scale_x, scale_y);
+    hipLaunchKernelGGL(frame_resize_kernel, dim3(resize_blocks((int64_t)N * 3 * H * W)), dim3(256), 0, st, frames_hwc, (const int32_t*)minmax,
+                       out_nchw, N, H0, W0, H, W, resize_scale(W, W0), resize_scale(H, H0));
     GN_LAUNCH_CHECK("frames_preprocess.resize");
     return 0;
 }

@@ -954,3 +954,43 @@ def rows_scatter(block, table, nrows, cursor):
     row_bytes = table[0].numel() * table.element_size() if table.dim() > 1 else table.element_size()
     _req(block.numel() * block.element_size() == row_bytes * nrows, "rows_scatter: argument check failed: block.numel() * block.element_size() == row_bytes * nrows")
     check(lib().goalnet_rows_scatter(block.data_ptr(), table.data_ptr(), row_bytes, nrows, _ctr(cursor), _s()), "rows_scatter")
+
+
+# ---- inference mode around the model (csrc/summary.hip) ---------------------------------------------------------------------
+def frames_preprocess_strided(frames, stride, out, minmax):
+    """out (n, 3, H, W) fp32 = frames_preprocess of frames[::stride], n = ceil(n_total / stride), read in place from the whole
+    video `frames` (n_total, H0, W0, 3) uint8; minmax: int32 scratch (n, 2)"""
+    _chk(frames, out, minmax)
+    _req(frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(),
+         "frames_preprocess_strided: frames must be contiguous uint8 (n_total, H0, W0, 3)")
+    n_total, h0, w0, _ = frames.shape
+    _req(stride >= 1 and n_total >= 1, "frames_preprocess_strided: stride and n_total must be >= 1")
+    n = (n_total + stride - 1) // stride
+    _req(out.dtype == F32 and out.dim() == 4 and out.shape[0] == n and out.shape[1] == 3 and out.is_contiguous(),
+         "frames_preprocess_strided: out must be contiguous fp32 (ceil(n_total / stride), 3, H, W)")
+    _req(minmax.dtype == torch.int32 and minmax.numel() == 2 * n and minmax.is_contiguous(), "frames_preprocess_strided: minmax must be int32 (n, 2)")
+    check(lib().goalnet_frames_preprocess_strided(frames.data_ptr(), n_total, int(stride), h0, w0, out.data_ptr(), out.shape[2], out.shape[3],
+                                                  minmax.data_ptr(), _s()), "frames_preprocess_strided")
+    return out
+
+
+def gather_clips(frames, change_points, selected, out, capacity, src_index, count, status):
+    """out[k] = the k-th frame of concatenate([frames[a:b] for the clips with selected != 0]) (end-exclusive slices); src_index[k] = its
+    source frame; count (int64[1]) = the number of frames, status (int32[1]) != 0 when it exceeds `capacity` (then nothing is written
+    past out[:capacity]). frames (full_n, ...) and out (>= capacity, ...) are contiguous uint8 with the same frame shape."""
+    _chk(frames, change_points, selected, out, src_index, status)
+    _req(frames.dtype == torch.uint8 and out.dtype == torch.uint8 and frames.is_contiguous() and out.is_contiguous() and frames.dim() >= 1
+         and frames.shape[0] >= 1 and tuple(frames.shape[1:]) == tuple(out.shape[1:]), "gather_clips: frames / out must be contiguous uint8 with one frame shape")
+    n_clips = selected.numel()
+    _req(change_points.dtype == torch.int32 and selected.dtype == torch.int32 and change_points.numel() == 2 * n_clips
+         and change_points.is_contiguous() and selected.is_contiguous(), "gather_clips: change_points int32 (n_clips, 2), selected int32 (n_clips)")
+    _req(0 <= capacity <= out.shape[0] and src_index.dtype == torch.int32 and src_index.numel() >= capacity and src_index.is_contiguous(),
+         "gather_clips: out and src_index must hold `capacity` frames")
+    _req(status.dtype == torch.int32 and status.numel() == 1, "gather_clips: status must be int32[1]")
+    frame_bytes = frames[0].numel()
+    nbytes = lib().goalnet_gather_clips_ws_bytes(n_clips)
+    ws = torch.empty(nbytes // 8, dtype=I64, device=frames.device)
+    check(lib().goalnet_gather_clips(frames.data_ptr(), frames.shape[0], frame_bytes, change_points.data_ptr(), selected.data_ptr(), n_clips,
+                                     out.data_ptr(), int(capacity), src_index.data_ptr(), _ctr(count), status.data_ptr(), ws.data_ptr(), nbytes, _s()),
+          "gather_clips")
+    return out

@@ -13,6 +13,11 @@ stays the reference's job — h5py is I/O, not the hot path) and run as a handfu
 points and annotator summaries resident on the device, so the per-epoch call is: predictions stay on the GPU, five
 small launches, 24 bytes back.
 
+`postprocess(..., full_frames = full_val_frames)` — the form `main.py --infer` calls (`main.py:336-345`), which also returns
+the summarised video `np.concatenate([full_frames[a:b] for the selected clips])` (`utils.py:634`) — is
+`SummaryEvaluator.summarize` / `summarize_video`: the frames of the selected clips are gathered on the device
+(csrc/summary.hip) right behind the knapsack, and the summary stays there.
+
 No CPU fallback: without the library / a GPU these functions raise.
 """
 from __future__ import annotations
@@ -22,7 +27,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import GoalnetError, check
 from .ops import _s
 
@@ -110,15 +115,19 @@ class SummaryEvaluator:
             self.n_users = int(gd.shape[0])
             self.gd = torch.as_tensor(np.ascontiguousarray(gd != 0).astype(np.uint8)).to(self.device)
         dev = self.device
-        self.mask = torch.empty(self.full_n, dtype=U8, device=dev)
-        self.selected = torch.empty(self.n_clips, dtype=I32, device=dev)
+        # one buffer, so that `summarize` reads everything back in one copy: [count int64 | gather status int32 | postprocess
+        # status int32 | selected int32[n_clips] | pad to 16 | mask uint8[full_n]]
+        self._mask_off = (16 + 4 * self.n_clips + 15) // 16 * 16
+        self._packed = torch.zeros(self._mask_off + self.full_n, dtype=U8, device=dev)
+        self.mask = self._packed[self._mask_off:]
+        self.selected = self._packed[16:16 + 4 * self.n_clips].view(I32)
         self.clip_values = torch.empty(self.n_clips, dtype=I64, device=dev)
         self.clip_lengths = torch.empty(self.n_clips, dtype=I32, device=dev)
         self.result = torch.zeros(3, dtype=F64, device=dev)           # [f_avg, f_max, status (int32 in the first 4 bytes)]
         self.ws_bytes = self.lib.goalnet_postprocess_ws_bytes(self.n_clips, self.cap_scaled, self.n_users)
         self.ws = torch.empty(self.ws_bytes // 8, dtype=I64, device=dev)
 
-    def _launch(self, batch_importances, with_fscore: bool):
+    def _launch(self, batch_importances, with_fscore: bool, status_ptr=None):
         pred = _importances_1d(batch_importances).detach().to(device=self.device, dtype=F32).contiguous()
         if pred.numel() < 1:
             raise IndexError("list index out of range")                 # expand_array on an empty list, utils.py:408
@@ -130,7 +139,8 @@ class SummaryEvaluator:
                 pred.data_ptr(), pred.numel(), self.skip, self.full_n, self.cps.data_ptr(), self.n_clips, 5, self.cap_scaled,
                 0 if gd is None else gd.data_ptr(), self.n_users if gd is not None else 0, self.mask.data_ptr(),
                 self.selected.data_ptr(), self.clip_values.data_ptr(), self.clip_lengths.data_ptr(),
-                0 if gd is None else self.result.data_ptr(), self.result[2:].data_ptr(), self.ws.data_ptr(), self.ws_bytes, _s()),
+                0 if gd is None else self.result.data_ptr(), self.result[2:].data_ptr() if status_ptr is None else status_ptr,
+                self.ws.data_ptr(), self.ws_bytes, _s()),
                 "postprocess")
 
     def _status(self, host):
@@ -144,6 +154,43 @@ class SummaryEvaluator:
         self._status(self.result.cpu())
         return torch.nonzero(self.selected).flatten().tolist(), self.mask.cpu().numpy()
 
+    def summarize(self, batch_importances, full_frames):
+        """utils.py:606-643 with `full_frames` given, the call of main.py:336-345. full_frames: (full_n_frames, H0, W0, C) uint8, on
+        the GPU or the host (then uploaded). Returns, in the reference's order, (summarized_video, summarized_video_frame_indices):
+        the frames of the selected clips `np.concatenate([full_frames[a:b] ...])` (utils.py:634, end-exclusive slices) as a uint8
+        tensor LEFT ON THE DEVICE, and the uint8 mask (utils.py:637-641, end-inclusive: one frame more per selected clip — the
+        reference's difference, kept). `last_src_index` (device int32) then holds the source frame of every summary frame and
+        `last_selected` the selected clip indices. The summary is a view of a buffer of `capacity = int(0.15 * full_n_frames)`
+        frames: the knapsack keeps sum(int(5 * len)) <= int(5 * capacity) and a clip's slice length is its knapsack weight when
+        the video has full_n_frames frames, so the bound is exact. Postprocess and gather are launched back to back; one
+        read-back fetches status, count, selection and mask."""
+        t = full_frames if torch.is_tensor(full_frames) else torch.from_numpy(np.ascontiguousarray(full_frames))
+        if t.dtype != U8 or t.dim() != 4:
+            raise ValueError("full_frames must be uint8 (full_n_frames, H0, W0, C)")
+        if t.shape[0] != self.full_n:
+            raise ValueError(f"full_frames holds {t.shape[0]} frames, the evaluator was built for {self.full_n}")
+        t = t.to(self.device).contiguous()
+        cap = self.capacity
+        out = torch.empty((max(cap, 1),) + tuple(t.shape[1:]), dtype=U8, device=self.device)
+        src_index = torch.empty(max(cap, 1), dtype=I32, device=self.device)
+        base = self._packed.data_ptr()
+        self._launch(batch_importances, with_fscore=False, status_ptr=base + 12)
+        with torch.cuda.device(self.device):
+            ops.gather_clips(t, self.cps, self.selected, out, cap, src_index, self._packed[0:8].view(I64), self._packed[8:12].view(I32))
+        host = self._packed.cpu()                                       # the one synchronising read-back
+        count = int(host[0:8].view(I64)[0])
+        gstatus, pstatus = host[8:16].view(I32).tolist()
+        if pstatus != 0:
+            raise IndexError(f"a selected clip interval reaches outside the video's {self.full_n} frames "
+                             "(utils.py:640 raises IndexError there)")
+        if gstatus != 0:
+            raise GoalnetError(f"the summary has {count} frames, more than the capacity of {cap}: change points overlap or leave the video")
+        self.last_selected = torch.nonzero(host[16:16 + 4 * self.n_clips].view(I32)).flatten().tolist()
+        if count == 0:
+            raise ValueError("need at least one array to concatenate")   # np.concatenate([]) at utils.py:634: no clip selected
+        self.last_src_index = src_index[:count]
+        return out[:count], host[self._mask_off:].numpy().copy()
+
     def __call__(self, batch_predictions) -> Tuple[float, float]:
         """utils.py:586-604: (f_score_avg, f_score_max). One 24-byte read-back."""
         self._launch(batch_predictions, with_fscore=True)
@@ -155,6 +202,12 @@ class SummaryEvaluator:
 def postprocess(batch_importances, change_points, skip_frames: int, full_n_frames: int, device=None):
     """utils.py:606-643 with the change points as an argument. Returns (selected clip indices, uint8 mask)."""
     return SummaryEvaluator(change_points, full_n_frames, skip_frames, None, device).postprocess(batch_importances)
+
+
+def summarize_video(batch_importances, change_points, skip_frames: int, full_n_frames: int, full_frames, device=None):
+    """utils.py:606-643 with `full_frames` given and the change points as an argument. Returns (summarized_video uint8 on the
+    device, uint8 mask): the reference's return order."""
+    return SummaryEvaluator(change_points, full_n_frames, skip_frames, None, device).summarize(batch_importances, full_frames)
 
 
 def postprocess_and_get_fscores(batch_predictions, full_n_batch_frames: int, gd_summarized_video_frame_indices, change_points,

@@ -12,25 +12,40 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import GoalnetError, check
 from .ops import _s
 
 
-def frames_to_tensor(frames, size=(40, 40), device=None) -> torch.Tensor:
+def frames_to_tensor(frames, size=(40, 40), device=None, stride: int = 1) -> torch.Tensor:
     """frames: (N, H0, W0, 3) uint8 (numpy or torch, BGR as cv2 decodes); size = (width, height) as `cv2.resize` takes it.
-    Returns the (N, 3, height, width) float32 GPU tensor of utils.py:291."""
+    Returns the (N, 3, height, width) float32 GPU tensor of utils.py:291.
+    stride > 1: `frames` is the whole decoded video and every stride-th frame is kept (`count % skip_frames == 0`,
+    utils.py:283): the ceil(N / stride) frames 0, stride, 2 stride, ... are read in place from a video that is resident on the
+    GPU (no `frames[::stride].contiguous()` copy; csrc/summary.hip), bit-identical to the stride-1 call on that copy. A host
+    array is sliced before the upload instead."""
     if not torch.cuda.is_available():
         raise GoalnetError("frame pre-processing runs on the GPU (torch.cuda.is_available() is False); there is no CPU fallback")
     dev = torch.device(device if device is not None else "cuda:0")
     t = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
     if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
         raise ValueError("frames must be uint8 (N, H0, W0, 3)")
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    if stride > 1 and not t.is_cuda:
+        t, stride = t[::stride], 1                                      # upload the kept frames only
     t = t.to(dev).contiguous()
     n, h0, w0, _ = t.shape
     if n < 1:
         raise ValueError("no frames")
     w, h = int(size[0]), int(size[1])
+    if stride > 1:
+        n_out = (n + stride - 1) // stride
+        out = torch.empty(n_out, 3, h, w, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ops.frames_preprocess_strided(t, stride, out, torch.empty(n_out, 2, dtype=torch.int32, device=dev))
+        return out
     out = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
     scratch = torch.empty(n, 2, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):

@@ -1,0 +1,105 @@
+"""The reference's inference mode (`main.py --infer`, `/root/reference/main.py:300-348`) on the GPU: a decoded video goes in,
+its summary comes out.
+
+    video_frames, full_n = extract_condensed_frame_tensor(video_fp, skip_frames = 60)       # main.py:315  (decodes the file)
+    full_val_frames = get_frame_tensor(video_fp)                                            # main.py:317  (decodes it again)
+    audio_features_tensor = extract_audio_features(audio_fp, n_frames = N)                  # main.py:321
+    val_predictions = frame_importance_model(val_audios, val_frames)                        # main.py:331
+    summarized_video, summarized_video_frame_indices = postprocess(..., full_frames = full_val_frames)   # main.py:336-345
+
+`VideoSummarizer` runs these lines on ONE decoded copy of the video that is resident in device memory: every skip_frames-th
+frame is normalised and resized in place (csrc/summary.hip, no second decode and no contiguous copy of the kept frames), the
+model runs on the whole video, the knapsack picks the clips and their frames are gathered into the summary on the device. One
+host synchronisation per video. Decoding (`cv2.VideoCapture`) and `export_video` stay the reference's I/O.
+
+No CPU fallback: without the library / a GPU the call raises.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List
+
+import numpy as np
+import torch
+
+from .postprocess import SummaryEvaluator
+from .preprocess import SR, extract_audio_features, frames_to_tensor
+
+
+@dataclass
+class VideoSummary:
+    frames: torch.Tensor           # (count, H0, W0, C) uint8 on the device: the summarised video (utils.py:634)
+    frame_indices: np.ndarray      # (full_n,) uint8 mask: summarized_video_frame_indices (utils.py:637-641, end-inclusive)
+    selected: List[int]            # indices of the selected clips (rows of change_points)
+    src_index: torch.Tensor        # (count,) int32 on the device: the source frame of every summary frame
+    predictions: torch.Tensor      # (N, 1) float32 on the device: the model's importance of every sampled frame
+
+
+class VideoSummarizer:
+    """`VideoSummarizer(model, change_points, skip_frames=60, size=(40, 40))(full_frames, ...)` = main.py:315-345.
+
+    model: an `AVM` with the regression head; change_points: the video's [n_clips][2] KTS change points (read from the dataset's
+    HDF5 file by the caller, as for `SummaryEvaluator`); skip_frames: main.py:311; size: the (width, height) of utils.py:285.
+
+    The model runs under `no_grad` IN ITS CURRENT MODE. The reference never calls `.eval()` (main.py:325-331), so there — and here
+    with a model left in train mode — BatchNorm normalises with the statistics of the whole video and updates its running
+    buffers, and dropout is active. Call `model.eval()` first for a summary that depends on the checkpoint alone; that is the
+    recommended use."""
+
+    def __init__(self, model, change_points, skip_frames: int = 60, size=(40, 40)):
+        if getattr(model, "head", "regression") != "regression":
+            raise ValueError("VideoSummarizer needs the regression head: post-processing takes one importance per frame")
+        cps = np.asarray(change_points)
+        if cps.ndim != 2 or cps.shape[1] != 2 or cps.shape[0] < 1:
+            raise ValueError("change_points must be [n_clips][2]")
+        if int(skip_frames) < 1:
+            raise ValueError("skip_frames must be positive")
+        self.model = model
+        self.change_points = cps
+        self.skip_frames = int(skip_frames)
+        self.size = (int(size[0]), int(size[1]))
+        self._evaluators = {}          # full_n -> SummaryEvaluator (change points and buffers stay resident between videos)
+
+    def _evaluator(self, full_n: int) -> SummaryEvaluator:
+        ev = self._evaluators.get(full_n)
+        if ev is None:
+            self._evaluators.clear()
+            ev = self._evaluators[full_n] = SummaryEvaluator(self.change_points, full_n, self.skip_frames, None, self.model._device)
+        return ev
+
+    def __call__(self, full_frames, audio_features=None, waveform=None, sr: int = SR, bin_length=None) -> VideoSummary:
+        """full_frames: (full_n, H0, W0, 3) uint8, the decoded video (`get_frame_tensor`, utils.py:294-305), on the GPU or the host.
+        With `audio_included=True` give either audio_features (N, 30, B) for the N = ceil(full_n / skip_frames) sampled frames, or
+        the decoded `waveform` at `sr` together with `bin_length` (the reference's own call at main.py:321 omits bin_length and
+        cannot run, so nothing is guessed)."""
+        model = self.model
+        t = full_frames if torch.is_tensor(full_frames) else torch.from_numpy(np.ascontiguousarray(full_frames))
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+            raise ValueError("full_frames must be uint8 (full_n, H0, W0, 3) with at least one frame")
+        full_n = int(t.shape[0])
+        n = (full_n + self.skip_frames - 1) // self.skip_frames
+        if model.audio_included:
+            if audio_features is None and waveform is None:
+                raise ValueError("audio_included=True needs audio_features or a waveform")
+            if audio_features is None and bin_length is None:
+                raise ValueError("a waveform needs bin_length (utils.extract_audio_features(audio_fp, n_frames, bin_length))")
+            if audio_features is not None:
+                audio_features = audio_features if torch.is_tensor(audio_features) else torch.as_tensor(np.asarray(audio_features))
+                if audio_features.dim() != 3 or audio_features.shape[0] != n:
+                    raise ValueError(f"audio_features must be (N, 30, B) with N = {n} sampled frames, got {tuple(audio_features.shape)}")
+        model._require_device()
+        dev = model._device
+        t = t.to(dev).contiguous()
+        with torch.cuda.device(dev), torch.no_grad():
+            visual = frames_to_tensor(t, self.size, dev, stride=self.skip_frames)
+            audio = None
+            if model.audio_included:
+                if audio_features is not None:
+                    audio = audio_features.detach().to(device=dev, dtype=torch.float32).contiguous()
+                else:
+                    audio = extract_audio_features(waveform, n, int(bin_length), sr, dev)
+            out, _ = model.forward_device(audio, visual, save=False)
+            predictions = out.view(-1, 1)
+            ev = self._evaluator(full_n)
+            frames, mask = ev.summarize(predictions, t)
+        return VideoSummary(frames, mask, ev.last_selected, ev.last_src_index, predictions)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GOALNET_ABI_VERSION 5
+#define GOALNET_ABI_VERSION 6
 
 #define GOALNET_OK 0
 #define GOALNET_E_NULL (-1)      /* required pointer is NULL */
@@ -454,6 +454,26 @@ int goalnet_postprocess(const float* pred, int n_sampled, int skip_frames, int f
  * minmax: scratch int32 [N][2]. PARITY UNPINNED (OpenCV absent from the build image). */
 int goalnet_frames_preprocess(const uint8_t* frames_hwc, int N, int H0, int W0, float* out_nchw, int H, int W,
                               int32_t* minmax, void* stream);
+
+/* ---- inference mode (main.py:300-348) around the model, for a decoded video resident in device memory ---------------------
+ * goalnet_frames_preprocess of every frame_stride-th frame (extract_condensed_frame_tensor keeps count % skip_frames == 0,
+ * utils.py:281-287) WITHOUT a contiguous copy of those frames: frames_hwc is the whole video, uint8 [n_total][H0][W0][3];
+ * out_nchw: float32 [n][3][H][W] and minmax: scratch int32 [n][2] with n = ceil(n_total / frame_stride); output i comes from frame
+ * i * frame_stride. Bit-identical to goalnet_frames_preprocess on the contiguous copy (the same per-pixel code, integer min / max).
+ * Any frame size and base alignment: the min / max pass reads 16 bytes per lane between a frame's 16-byte boundaries. */
+int goalnet_frames_preprocess_strided(const uint8_t* frames_hwc, int n_total, int frame_stride, int H0, int W0, float* out_nchw,
+                                      int H, int W, int32_t* minmax, void* stream);
+/* The summarised video of utils.py:634, np.concatenate([full_frames[a:b] for the selected clips]): for every clip c with
+ * selected[c] != 0 (the flags goalnet_postprocess writes), in clip order, frames [a, min(b, full_n)) of frames [full_n][frame_bytes]
+ * are copied to `out` back to back — a Python slice, end EXCLUSIVE, whereas the mask of goalnet_postprocess is end inclusive
+ * (the reference's difference, kept). src_index[k] = source frame of summary frame k; *count (device int64) = the number of summary
+ * frames; *status (device int32) != 0 when that exceeds out_capacity_frames: then only the first out_capacity_frames frames (and
+ * src_index entries) are written, nothing past the buffer. With capacity int(0.15 * full_n) the knapsack's budget rules that out.
+ * 16-byte copies when frame_bytes, frames and out are multiples of 16, else 4-byte or single-byte ones. ws: goalnet_gather_clips_ws_bytes. */
+size_t goalnet_gather_clips_ws_bytes(int n_clips);
+int goalnet_gather_clips(const uint8_t* frames, int full_n, int64_t frame_bytes, const int32_t* change_points, const int32_t* selected,
+                         int n_clips, uint8_t* out, int64_t out_capacity_frames, int32_t* src_index, int64_t* count, int32_t* status,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /* up to GOALNET_ROWCOPY_MAX gathers (gather != 0: dst[0:nrows] = src[c : c + nrows]) and scatters
  * (gather == 0: dst[c : c + nrows] = src[0:nrows]) in one launch; c = *cursor + cursor_bias */

@@ -10,5 +10,6 @@ from ._lib import GoalnetError, LIB_PATH  # noqa: F401
 from .avm import AVM  # noqa: F401
 from . import optim  # noqa: F401
 from .summarize import VideoSummarizer, VideoSummary  # noqa: F401
+from . import groundtruth  # noqa: F401
 
-__all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "VideoSummarizer", "VideoSummary"]
+__all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "VideoSummarizer", "VideoSummary", "groundtruth"]

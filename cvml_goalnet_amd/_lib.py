@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GOALNET_LIB_PATH") or os.path.join(_HERE, "libgoalnet_hip.so")   # override: A/B builds of the kernels
-ABI_VERSION = 6
+ABI_VERSION = 7
 STAT_PARTS = 1024
 
 P = c_void_p  # device pointers and the stream travel as void*
@@ -146,6 +146,10 @@ PROTOTYPES = {
     "goalnet_fscore": (c_int, [P, P, c_int, c_int, P, P, P]),
     "goalnet_postprocess_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "goalnet_postprocess": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "goalnet_postprocess_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "goalnet_postprocess_batch": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "goalnet_postprocess_batch_kernel_name": (c_char_p, [c_int, c_int]),
+    "goalnet_mean_annotations": (c_int, [P, c_int, c_int, c_int, P, P, P]),
     "goalnet_rows_gather": (c_int, [P, P, c_int64, c_int, P, P]),
     "goalnet_rows_scatter": (c_int, [P, P, c_int64, c_int, P, P]),
 }

@@ -91,7 +91,8 @@ def get_fscore(gd_summary_indices, predicted_summary_indices, device=None) -> Tu
 
 class SummaryEvaluator:
     """One video's static inputs (change points from the dataset's HDF5 file, annotator summaries, frame counts) kept on
-    the device; `__call__(pred)` = postprocess_and_get_fscores, `postprocess(pred)` = postprocess."""
+    the device; `__call__(pred)` = postprocess_and_get_fscores, `postprocess(pred)` = postprocess. `postprocess_batch` /
+    `fscores_batch` take B importance vectors of the video per call; `from_annotations` builds `gd` on the device."""
 
     def __init__(self, change_points, full_n_frames: int, skip_frames: int, gd_summarized_video_frame_indices=None, device=None):
         self.device = _dev(device)
@@ -109,6 +110,7 @@ class SummaryEvaluator:
         self.cap_scaled = int(self.capacity * 5)                       # utils.py:478 (scale_factor = 5)
         self.gd = None
         self.n_users = 0
+        self._batch_cap = 0                                            # batch buffers: allocated on first use, grown when B grows
         if gd_summarized_video_frame_indices is not None:
             gd = np.asarray(gd_summarized_video_frame_indices)
             assert gd.ndim == 2 and gd.shape[1] == self.full_n, "gd_summary_indices must be (n_users, full_n_frames)"
@@ -126,6 +128,103 @@ class SummaryEvaluator:
         self.result = torch.zeros(3, dtype=F64, device=dev)           # [f_avg, f_max, status (int32 in the first 4 bytes)]
         self.ws_bytes = self.lib.goalnet_postprocess_ws_bytes(self.n_clips, self.cap_scaled, self.n_users)
         self.ws = torch.empty(self.ws_bytes // 8, dtype=I64, device=dev)
+
+    @classmethod
+    def from_annotations(cls, change_points, full_n_frames: int, skip_frames: int, user_anno, device=None):
+        """The evaluator of a video from its raw annotator scores `user_anno` (A, full_n_frames) — `load_mat_file`'s output,
+        utils.py:102: the A annotator summaries of utils.py:103-118 are one batched call (A knapsacks on A CUs) whose masks
+        become `gd` on the device; nothing returns to the host. Ready for `__call__` afterwards."""
+        ev = cls(change_points, full_n_frames, skip_frames, None, device)
+        _, masks = ev.postprocess_batch(user_anno, to_host=False)
+        ev.gd = masks
+        ev.n_users = int(masks.shape[0])
+        ev.ws_bytes = ev.lib.goalnet_postprocess_ws_bytes(ev.n_clips, ev.cap_scaled, ev.n_users)
+        ev.ws = torch.empty(ev.ws_bytes // 8, dtype=I64, device=ev.device)
+        ev._batch_cap = 0                                              # the batch workspace depends on n_users as well
+        return ev
+
+    def _importances_2d(self, importances) -> torch.Tensor:
+        """(B, n) float32 on the device from (B, n), (B, n, 1) or a list of B vectors of one length (each as utils.py:608-610
+        takes it). A float64 input is rounded in float64 first, as `torch.round` at utils.py:611 rounds it: the float32 image
+        of 2.5 + 1e-9 is 2.5, which would round the other way."""
+        if torch.is_tensor(importances):
+            t = importances
+        elif isinstance(importances, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(importances))
+        else:
+            rows = [_importances_1d(r) for r in importances]
+            if len(rows) == 0 or any(r.shape != rows[0].shape for r in rows):
+                raise ValueError("postprocess_batch: need B >= 1 importance vectors of one length")
+            t = torch.stack([r.detach().to(self.device) for r in rows])
+        if t.dim() == 3:
+            assert t.shape[-1] == 1, "E: Invalid shape for importance tensor"
+            t = t[:, :, 0]
+        assert t.dim() == 2, "E: Invalid shape for importance tensor"
+        if t.shape[0] < 1:
+            raise ValueError("postprocess_batch: need B >= 1 importance vectors")
+        if t.shape[1] < 1:
+            raise IndexError("list index out of range")                 # expand_array on an empty list, utils.py:408
+        t = t.detach().to(self.device)
+        if t.dtype == F64:
+            t = torch.round(t)
+        return t.to(F32).contiguous()
+
+    def _batch_buffers(self, B: int):
+        if B > self._batch_cap:
+            dev = self.device
+            self._b_mask = torch.empty((B, self.full_n), dtype=U8, device=dev)
+            self._b_selected = torch.empty((B, self.n_clips), dtype=I32, device=dev)
+            self._b_values = torch.empty((B, self.n_clips), dtype=I64, device=dev)
+            self._b_lengths = torch.empty((B, self.n_clips), dtype=I32, device=dev)
+            self._b_result = torch.zeros(2 * B + (B + 1) // 2, dtype=F64, device=dev)   # [fscore [B][2] | status int32 [B]]: one read-back
+            self._b_ws_bytes = self.lib.goalnet_postprocess_batch_ws_bytes(self.n_clips, self.cap_scaled, self.n_users, B)
+            self._b_ws = torch.empty(max(self._b_ws_bytes // 8, 1), dtype=I64, device=dev)
+            self._batch_cap = B
+
+    def _launch_batch(self, importances, with_fscore: bool) -> int:
+        pred = self._importances_2d(importances)
+        B = int(pred.shape[0])
+        gd = self.gd if with_fscore else None
+        if with_fscore and gd is None:
+            raise ValueError("this evaluator was built without annotator summaries")
+        self._batch_buffers(B)
+        cap = self._batch_cap
+        with torch.cuda.device(self.device):
+            check(self.lib.goalnet_postprocess_batch(
+                pred.data_ptr(), B, int(pred.shape[1]), self.skip, self.full_n, self.cps.data_ptr(), self.n_clips, 5, self.cap_scaled,
+                0 if gd is None else gd.data_ptr(), self.n_users if gd is not None else 0, self._b_mask.data_ptr(),
+                self._b_selected.data_ptr(), self._b_values.data_ptr(), self._b_lengths.data_ptr(),
+                0 if gd is None else self._b_result.data_ptr(), self._b_result[2 * cap:].data_ptr(),
+                self._b_ws.data_ptr(), self._b_ws_bytes, _s()),
+                "postprocess_batch")
+        return B
+
+    def _status_batch(self, host, B: int):
+        bad = torch.nonzero(host[2 * self._batch_cap:].view(torch.int32)[:B]).flatten().tolist()
+        if bad:
+            raise IndexError(f"item {bad[0]} of the batch: a selected clip interval reaches outside the video's {self.full_n} frames "
+                             f"(utils.py:640 raises IndexError there; items with that status: {bad})")
+
+    def postprocess_batch(self, importances, to_host: bool = True):
+        """`postprocess` (utils.py:606-643, full_frames = None) for B importance vectors of this video in one call: B knapsacks
+        on B CUs. Returns (list of B lists of selected clip indices, (B, full_n_frames) uint8 masks — a numpy array, or a
+        device tensor when to_host is False). `batch_clip_values` / `batch_clip_lengths` then hold get_clip_information per item."""
+        B = self._launch_batch(importances, with_fscore=False)
+        self._status_batch(self._b_result.cpu(), B)
+        sel = self._b_selected[:B].cpu()
+        self.batch_clip_values, self.batch_clip_lengths = self._b_values[:B], self._b_lengths[:B]
+        selected = [torch.nonzero(row).flatten().tolist() for row in sel]
+        masks = self._b_mask[:B]
+        return selected, (masks.cpu().numpy() if to_host else masks.clone())
+
+    def fscores_batch(self, predictions) -> Tuple[np.ndarray, np.ndarray]:
+        """`__call__` (utils.py:586-604) for B prediction vectors of this video: (f_score_avg [B], f_score_max [B]) float64,
+        one read-back."""
+        B = self._launch_batch(predictions, with_fscore=True)
+        host = self._b_result.cpu()
+        self._status_batch(host, B)
+        f = host[:2 * B].view(B, 2).numpy()
+        return f[:, 0].copy(), f[:, 1].copy()
 
     def _launch(self, batch_importances, with_fscore: bool, status_ptr=None):
         pred = _importances_1d(batch_importances).detach().to(device=self.device, dtype=F32).contiguous()

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GOALNET_ABI_VERSION 6
+#define GOALNET_ABI_VERSION 7
 
 #define GOALNET_OK 0
 #define GOALNET_E_NULL (-1)      /* required pointer is NULL */
@@ -447,6 +447,25 @@ int goalnet_postprocess(const float* pred, int n_sampled, int skip_frames, int f
                         int n_clips, int weight_scale, int capacity_scaled, const uint8_t* gd, int n_users, uint8_t* mask,
                         int32_t* selected, int64_t* clip_values, int32_t* clip_lengths, double* fscore, int32_t* status,
                         void* ws, size_t ws_bytes, void* stream);
+/* goalnet_postprocess for `batch` importance vectors of ONE video in one call (the 20 annotators of utils.py:102-118, the
+ * 10 models of baseline.py): pred [batch][n_sampled], mask [batch][full_n_frames], selected / clip_values / clip_lengths
+ * [batch][n_clips], status [batch], fscore [batch][2] (or NULL together with gd; gd [n_users][full_n_frames] is shared by
+ * the items). Item b receives exactly what goalnet_postprocess gives for row b. The knapsacks run as one block per item:
+ * the DP row stays on chip and the workspace holds one decision bit per table cell, not the int64 table.
+ * 1 <= batch <= 65535. No allocation, no synchronisation, capturable. */
+size_t goalnet_postprocess_batch_ws_bytes(int n_clips, int capacity_scaled, int n_users, int batch);
+int goalnet_postprocess_batch(const float* pred, int batch, int n_sampled, int skip_frames, int full_n_frames,
+                              const int32_t* change_points, int n_clips, int weight_scale, int capacity_scaled, const uint8_t* gd,
+                              int n_users, uint8_t* mask, int32_t* selected, int64_t* clip_values, int32_t* clip_lengths, double* fscore,
+                              int32_t* status, void* ws, size_t ws_bytes, void* stream);
+/* the knapsack kernel the dispatcher selects for these dims: the row in LDS up to 20 000 columns, two rolling rows in the
+ * workspace above (or when GOALNET_KNAPSACK_BATCH_ROLLING is set: A/B runs) */
+const char* goalnet_postprocess_batch_kernel_name(int n_clips, int capacity_scaled);
+/* get_annotations, utils.py:382-394: scores [n_annotators][full_n_frames] float32 -> labels_full [full_n_frames] =
+ * np.round(np.mean(scores[:, f])) (float32 mean in numpy's pairwise order for a 1-D array, round half to even) and
+ * labels_trimmed [ceil(full_n_frames / skip_frames)] = labels_full[0 :: skip_frames]. 1 <= n_annotators <= 128. */
+int goalnet_mean_annotations(const float* scores, int n_annotators, int full_n_frames, int skip_frames, float* labels_trimmed,
+                             float* labels_full, void* stream);
 
 /* ---- before the hot path: frame pre-processing of the loader.  utils.py:274-292 (decode excluded) -----------------
  * frames_hwc: device uint8 [N][H0][W0][3] (BGR as cv2 decodes); out_nchw: float32 [N][3][H][W] = per-frame min-max

@@ -720,7 +720,8 @@ int goalnet_linear_fwd_bf16(const void* x_bf16, int64_t ldx, const void* w_bf16,
                             int M, int64_t K, int J, void* ws, size_t ws_bytes, int f16, void* stream) {
     GN_REQUIRE(x_bf16 && w_bf16 && y, GOALNET_E_NULL, "linear_fwd_bf16: null pointer");
     GN_REQUIRE(M > 0 && J > 0 && K > 0 && K < (1ll << 31) - 64, GOALNET_E_SHAPE, "linear_fwd_bf16: bad dims");
-    GN_REQUIRE(K % BKH == 0 && J % 4 == 0 && ldx % 8 == 0 && ldy % 4 == 0, GOALNET_E_SHAPE, "linear_fwd_bf16: K %% 64, J %% 4, ldx %% 8");
+    GN_REQUIRE(K % BKH == 0 && J % 4 == 0, GOALNET_E_SHAPE, "linear_fwd_bf16: K %% 64, J %% 4");
+    GN_REQUIRE(ldx % 8 == 0 && ldy % 4 == 0, GOALNET_E_ALIGN, "linear_fwd_bf16: leading dimensions must be multiples of 16 bytes (ldx %% 8, ldy %% 4)");
     GN_REQUIRE(aligned16(x_bf16) && aligned16(w_bf16) && aligned16(y), GOALNET_E_ALIGN, "linear_fwd_bf16: alignment");
     hipStream_t st = (hipStream_t)stream;
     if (linear_use_256(M, K, J)) {
@@ -936,7 +937,8 @@ int goalnet_linear_bwd_dx_bf16(const void* dy_bf16, int64_t lddy, const void* w_
                                float* dx, int64_t lddx, int M, int64_t K, int J, int f16, void* stream) {
     GN_REQUIRE(dy_bf16 && w_bf16 && dx, GOALNET_E_NULL, "linear_bwd_dx_bf16: null pointer");
     GN_REQUIRE(M > 0 && J > 0 && K > 0 && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dx_bf16: bad dims");
-    GN_REQUIRE(J % BKH == 0 && K % 8 == 0 && lddy % 8 == 0 && lddx % 4 == 0, GOALNET_E_SHAPE, "linear_bwd_dx_bf16: J %% 64, K %% 8");
+    GN_REQUIRE(J % BKH == 0 && K % 8 == 0, GOALNET_E_SHAPE, "linear_bwd_dx_bf16: J %% 64, K %% 8");
+    GN_REQUIRE(lddy % 8 == 0 && lddx % 4 == 0, GOALNET_E_ALIGN, "linear_bwd_dx_bf16: leading dimensions must be multiples of 16 bytes (lddy %% 8, lddx %% 4)");
     GN_REQUIRE(aligned16(dy_bf16) && aligned16(w_bf16) && aligned16(dx), GOALNET_E_ALIGN, "linear_bwd_dx_bf16: alignment");
     if (!mult && linear_use_256(M, K, J))
         return launch_linear_dx_bf16_256("linear_bwd_dx_bf16(256)", (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)w_bf16, M, K,
@@ -957,7 +959,8 @@ int goalnet_linear_bwd_dx_bf16_o16(const void* dy_bf16, int64_t lddy, const void
                                    int M, int64_t K, int J, int f16, void* stream) {
     GN_REQUIRE(dy_bf16 && w_bf16 && dx_bf16, GOALNET_E_NULL, "linear_bwd_dx_bf16_o16: null pointer");
     GN_REQUIRE(M > 0 && J > 0 && K > 0 && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dx_bf16_o16: bad dims");
-    GN_REQUIRE(J % BKH == 0 && K % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0, GOALNET_E_SHAPE, "linear_bwd_dx_bf16_o16: J %% 64, K %% 8, lddx %% 8");
+    GN_REQUIRE(J % BKH == 0 && K % 8 == 0, GOALNET_E_SHAPE, "linear_bwd_dx_bf16_o16: J %% 64, K %% 8");
+    GN_REQUIRE(lddy % 8 == 0 && lddx % 8 == 0, GOALNET_E_ALIGN, "linear_bwd_dx_bf16_o16: leading dimensions must be multiples of 16 bytes (lddy %% 8, lddx %% 8)");
     GN_REQUIRE(aligned16(dy_bf16) && aligned16(w_bf16) && aligned16(dx_bf16), GOALNET_E_ALIGN, "linear_bwd_dx_bf16_o16: alignment");
     GN_REQUIRE(goalnet_linear_bwd_dx_bf16_o16_ok(M, K, J), GOALNET_E_SHAPE,
                "linear_bwd_dx_bf16_o16: dims not served (ask goalnet_linear_bwd_dx_bf16_o16_ok; use goalnet_linear_bwd_dx_bf16)");
@@ -970,7 +973,8 @@ int goalnet_linear_bwd_dw_bf16(const void* dy_bf16, int64_t lddy, const void* x_
                                int M, int64_t K, int J, int f16, void* stream) {
     GN_REQUIRE(dy_bf16 && x_bf16 && dw, GOALNET_E_NULL, "linear_bwd_dw_bf16: null pointer");
     GN_REQUIRE(M > 0 && J > 0 && K > 0 && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dw_bf16: bad dims");
-    GN_REQUIRE(J % 8 == 0 && K % 8 == 0 && lddy % 8 == 0 && ldx % 8 == 0, GOALNET_E_SHAPE, "linear_bwd_dw_bf16: J, K, lds %% 8");
+    GN_REQUIRE(J % 8 == 0 && K % 8 == 0, GOALNET_E_SHAPE, "linear_bwd_dw_bf16: J, K %% 8");
+    GN_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0, GOALNET_E_ALIGN, "linear_bwd_dw_bf16: leading dimensions must be multiples of 16 bytes (lddy %% 8, ldx %% 8)");
     GN_REQUIRE(aligned16(dy_bf16) && aligned16(x_bf16) && aligned16(dw), GOALNET_E_ALIGN, "linear_bwd_dw_bf16: alignment");
     {
         // >= 256 output rows, a reduction of at least 4 K-tiles and an output wide enough to fill the chip with 256^2 tiles

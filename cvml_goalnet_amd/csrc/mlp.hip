@@ -341,7 +341,8 @@ int goalnet_mlp_fwd(const float* cat, int64_t ldcat, int K0, const float* const*
                     float* logit, float* out, const float* labels, float* loss, float* dout, int n, int* sync, void* stream) {
     GN_REQUIRE(cat && w && b && mask && ldmask && h && mult && logit && out && sync, GOALNET_E_NULL, "mlp_fwd: null pointer");
     GN_REQUIRE(n >= 1 && n <= 16, GOALNET_E_SHAPE, "mlp_fwd: 1..16 rows (the reference's sub-batches)");
-    GN_REQUIRE(K0 > 0 && K0 <= KMAX && K0 % 4 == 0 && ldcat % 4 == 0 && aligned16(cat), GOALNET_E_SHAPE, "mlp_fwd: K0 must be a multiple of 4, <= 640");
+    GN_REQUIRE(K0 > 0 && K0 <= KMAX && K0 % 4 == 0, GOALNET_E_SHAPE, "mlp_fwd: K0 must be a multiple of 4, <= 640");
+    GN_REQUIRE(ldcat % 4 == 0 && aligned16(cat), GOALNET_E_ALIGN, "mlp_fwd: cat and its row stride must be 16-byte aligned");
     MlpFwdP P;
     P.x0 = cat; P.ldx0 = ldcat; P.K0 = K0;
     const int J[4] = {512, 512, 256, 128};
@@ -379,9 +380,10 @@ int goalnet_mlp_bwd(const float* dout, const float* out, const float* const* x, 
                     int n, int K0, void* ws, size_t ws_bytes, int* sync, void* stream) {
     GN_REQUIRE(dout && out && x && m && w && dw && db && dcat && ws && sync, GOALNET_E_NULL, "mlp_bwd: null pointer");
     GN_REQUIRE(n >= 1 && n <= 16, GOALNET_E_SHAPE, "mlp_bwd: 1..16 rows (the reference's sub-batches)");
-    GN_REQUIRE(K0 > 0 && K0 <= KMAX && K0 % 4 == 0 && ldcat % 4 == 0 && lddcat % 4 == 0 && ldmcat % 4 == 0 && voff % 4 == 0 && voff >= 0 && voff < K0,
-               GOALNET_E_SHAPE, "mlp_bwd: K0 / leading dims / voff must be multiples of 4");
-    GN_REQUIRE(ws_bytes >= goalnet_mlp_bwd_ws_bytes(n) && aligned16(ws) && aligned16(dcat) && aligned16(db5), GOALNET_E_WORKSPACE, "mlp_bwd: workspace too small or misaligned");
+    GN_REQUIRE(K0 > 0 && K0 <= KMAX && K0 % 4 == 0 && voff % 4 == 0 && voff >= 0 && voff < K0, GOALNET_E_SHAPE, "mlp_bwd: K0 / voff must be multiples of 4");
+    GN_REQUIRE(ldcat % 4 == 0 && lddcat % 4 == 0 && ldmcat % 4 == 0 && aligned16(ws) && aligned16(dcat) && aligned16(db5), GOALNET_E_ALIGN,
+               "mlp_bwd: leading dimensions, ws, dcat and db5 must be 16-byte aligned");
+    GN_REQUIRE(ws_bytes >= goalnet_mlp_bwd_ws_bytes(n), GOALNET_E_WORKSPACE, "mlp_bwd: workspace too small");
     MlpBwdP P;
     P.dout = dout; P.out = out; P.ldx0 = ldcat; P.ldm0 = ldmcat;
     const int J[4] = {512, 512, 256, 128};

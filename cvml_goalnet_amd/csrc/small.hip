@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256) void grad_finite_check_kernel(const float* __r
     bool bad = false;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = g[i];
-        bad |= !(fabsf(v) <= 3.0e38f);                 // inf or nan
+        bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;       // inf or nan: exponent all ones (FLT_MAX is finite)
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) {
         const unsigned long long t = (unsigned long long)(*step + step_bias);
@@ -504,6 +504,10 @@ int goalnet_conv1d_bwd(const float* x, const float* dz, const float* w, float* d
     const int Lo = (L + 2 * pad - 3) / stride + 1;
     hipStream_t st = (hipStream_t)stream;
     const bool many = N >= 64;          // few frames (the reference's sub-batches): lanes split the channels; many: lanes split the frames
+    const size_t need = goalnet_conv1d_bwd_ws_bytes(N, Cin, Cout);
+    // a workspace that is lent must be whole (ws = NULL: no frame slices); both checks precede the first launch
+    GN_REQUIRE(!ws || ws_bytes >= need, GOALNET_E_WORKSPACE, "conv1d_bwd: workspace too small");
+    GN_REQUIRE(!(ws && need) || (reinterpret_cast<uintptr_t>(ws) & 7u) == 0, GOALNET_E_ALIGN, "conv1d_bwd: workspace must be 8-byte aligned");
     if (dx) {
         if (many)
             hipLaunchKernelGGL(conv1d_dx_big_kernel, dim3(grid1d((int64_t)N * Cin * L)), dim3(256), 0, st, dz, w, dx, N, Cin, L, Cout, Lo, stride, pad);
@@ -512,9 +516,7 @@ int goalnet_conv1d_bwd(const float* x, const float* dz, const float* w, float* d
         GN_LAUNCH_CHECK("conv1d_bwd.dx");
     }
     if (many) {
-        const size_t need = goalnet_conv1d_bwd_ws_bytes(N, Cin, Cout);
-        const int slices = need && ws && ws_bytes >= need ? CONV1D_DW_SLICES : 1;
-        GN_REQUIRE(slices == 1 || (reinterpret_cast<uintptr_t>(ws) & 7u) == 0, GOALNET_E_ALIGN, "conv1d_bwd: workspace must be 8-byte aligned");
+        const int slices = need && ws ? CONV1D_DW_SLICES : 1;
         hipLaunchKernelGGL(conv1d_dw_big_kernel, dim3(((Cout + 3) / 4) * ((Cin + 3) / 4), slices), dim3(256), 0, st, x, dz, dw, (double*)ws,
                            N, Cin, L, Cout, Lo, stride, pad);
         if (slices > 1) {

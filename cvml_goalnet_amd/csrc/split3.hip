@@ -320,7 +320,8 @@ int goalnet_linear_fwd_split(int parts, const void* xs, const void* wsp, const f
                              float* y, int64_t ldy, float* mult_out, int64_t ldmult, int M, int64_t K, int J, void* ws, size_t ws_bytes,
                              const int* oscale, void* stream) {
     GN_REQUIRE(xs && wsp && y && ws && (parts == 3 || oscale), GOALNET_E_NULL, "linear_fwd_split: null pointer (parts = 2 needs oscale)");
-    GN_REQUIRE(goalnet_linear_split_ok(parts, M, K, J) && ldy % 4 == 0, GOALNET_E_SHAPE, "linear_fwd_split: dims not served (goalnet_linear_split_ok)");
+    GN_REQUIRE(goalnet_linear_split_ok(parts, M, K, J), GOALNET_E_SHAPE, "linear_fwd_split: dims not served (goalnet_linear_split_ok)");
+    GN_REQUIRE(ldy % 4 == 0, GOALNET_E_ALIGN, "linear_fwd_split: ldy must be a multiple of 16 bytes");
     GN_REQUIRE(aligned16(xs) && aligned16(wsp) && aligned16(y) && aligned16(ws), GOALNET_E_ALIGN, "linear_fwd_split: alignment");
     GN_REQUIRE(ws_bytes >= goalnet_linear_fwd_split_ws_bytes(parts, M, K, J), GOALNET_E_WORKSPACE, "linear_fwd_split: workspace too small");
     hipStream_t st = (hipStream_t)stream;
@@ -336,7 +337,8 @@ int goalnet_linear_fwd_split(int parts, const void* xs, const void* wsp, const f
 int goalnet_linear_bwd_dx_split(int parts, const void* dys, const void* wsp, float* dx, int64_t lddx, int M, int64_t K, int J,
                                 const int* oscale, void* stream) {
     GN_REQUIRE(dys && wsp && dx && (parts == 3 || oscale), GOALNET_E_NULL, "linear_bwd_dx_split: null pointer (parts = 2 needs oscale)");
-    GN_REQUIRE(goalnet_linear_split_ok(parts, M, K, J) && lddx % 4 == 0 && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dx_split: dims not served");
+    GN_REQUIRE(goalnet_linear_split_ok(parts, M, K, J) && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dx_split: dims not served");
+    GN_REQUIRE(lddx % 4 == 0, GOALNET_E_ALIGN, "linear_bwd_dx_split: lddx must be a multiple of 16 bytes");
     GN_REQUIRE(aligned16(dys) && aligned16(wsp) && aligned16(dx), GOALNET_E_ALIGN, "linear_bwd_dx_split: alignment");
     return launch_linear_dx_split_256("linear_bwd_dx_split", parts, (const __hip_bfloat16*)dys, (const __hip_bfloat16*)wsp, M, K, J, dx, lddx,
                                       parts == 2 ? oscale : nullptr, (hipStream_t)stream);

@@ -649,6 +649,40 @@ class AVM(nn.Module):
         bn.num_batches_tracked += 1
         return p, idx, st
 
+    def _conv_block_fwd(self, i, x, st_in, n, hc, wc, cin, cout, save, ctx, p16, keep_split):
+        """Block i (2 or 3) of VisBl: 3 x 3 convolution (+ ReLU) of block i-1's pooled activation x (N,hc,wc,cin) with that block's
+        BatchNorm (st_in) folded into the operand load, then _bn_block. The convolution runs on one of three engines: 16-bit MFMA
+        (precision bf16 / fp16), split operands (bf16x6 / fp16x3 where _x6_conv says so) or fp32 MFMA.
+        p16: store the pooled activation in 16 bits; keep_split: backward reuses the split operand (ctx x{i-1}s, x{i-1}s_amax, x{i-1}s_gen).
+        Returns (p, idx, st, xh); xh is the padded 16-bit operand the weight gradient reads again, None on the other engines."""
+        dev, P, BF16 = self._device, self._pflat, self._h16
+        wname, bname, xk = f"visbl.conv{i}.weight", f"visbl.conv{i}.bias", f"x{i - 1}"
+        flops = 2.0 * n * hc * wc * 9 * cin * cout
+        # where p is kept in bf16 AND the 256 x 256 tile computes the convolution, the conv output is stored as bf16 too:
+        # rounding is monotonic, so the max-pool of the rounded values is the rounded max-pool (same p, same statistics);
+        # only ties in the argmax are broken differently
+        y16 = p16 and ops.conv3x3_fwd_bf16p_o16_ok(n, hc, wc, cin, cout)
+        y = torch.empty(n, hc, wc, cout, dtype=BF16 if y16 else F32, device=dev)
+        xh = None
+        if self._half:
+            xh = ops.to_bf16_padded(x, st_in[2], st_in[3], self._padbuf(xk if save else xk + "e", n, hc, wc, cin), n, hc, wc, cin)
+            wb = ops.cast_bf16(P(wname), torch.empty(cout * 9 * cin, dtype=BF16, device=dev))
+            self._timed("conv_fwd", flops, ops.conv3x3_fwd_bf16p_o16 if y16 else ops.conv3x3_fwd_bf16p,
+                        xh, wb, P(bname), True, y, n, hc, wc, cin, cout)
+        elif self._x6_conv(n * hc * wc, cout):
+            xs, ax = self._split_act(xk + ("s" if save else "se"), x, st_in[2], st_in[3], n, hc, wc, cin)
+            ws, aw = self._split_w(P(wname), cout * 9, cin)
+            self._timed("conv_fwd", flops, ops.conv3x3_fwd_split, self._parts,
+                        xs, ws, P(bname), True, y, n, hc, wc, cin, cout, self._osc(ax, aw))
+            if save and keep_split:
+                ctx.update({xk + "s": xs, xk + "s_amax": ax, xk + "s_gen": self._padgen[xk + "s"]})
+            del xs, ws
+        else:
+            self._timed("conv_fwd", flops, ops.conv3x3_fwd,
+                        x, st_in[2], st_in[3], P(wname), P(bname), True, y, n, hc, wc, cin, cout)
+        # the conv output is only an input of the pool: backward reads the ReLU mask off p (csrc/pool_bn.hip)
+        return (*self._bn_block(y, n, hc, wc, cout, i, save, p16=p16), xh)
+
     def forward_device(self, audio, visual, save: bool):
         """audio (N,30,B) / None, visual (N,3,H,W): contiguous fp32 GPU tensors. Returns out (N,) [, ctx]."""
         if visual.dim() != 4 or visual.shape[1] != 3:
@@ -699,56 +733,18 @@ class AVM(nn.Module):
         del y1          # the conv output is only an input of the pool: backward reads the ReLU mask off p (csrc/pool_bn.hip)
         bf = self._half
         BF16 = self._h16                 # the 16-bit storage format of this model (bfloat16 or float16)
-        # where p is kept in bf16 AND the 256 x 256 tile computes the convolution, the conv output is stored as bf16 too:
-        # rounding is monotonic, so the max-pool of the rounded values is the rounded max-pool (same p, same statistics);
-        # only ties in the argmax are broken differently
-        p16_2 = bf and self.act_bf16 and self._p16_ok(wp1, 256)
-        y16_2 = p16_2 and ops.conv3x3_fwd_bf16p_o16_ok(n, hp1, wp1, 64, 256)
-        y2 = torch.empty(n, hp1, wp1, 256, dtype=BF16 if y16_2 else F32, device=dev)
-        if bf:
-            xh1 = ops.to_bf16_padded(p1, st1[2], st1[3], self._padbuf("x1" if save else "x1e", n, hp1, wp1, 64), n, hp1, wp1, 64)
-            w2b = ops.cast_bf16(P("visbl.conv2.weight"), torch.empty(256 * 9 * 64, dtype=BF16, device=dev))
-            self._timed("conv_fwd", 2.0 * n * hp1 * wp1 * 576 * 256, ops.conv3x3_fwd_bf16p_o16 if y16_2 else ops.conv3x3_fwd_bf16p,
-                        xh1, w2b, P("visbl.conv2.bias"), True, y2, n, hp1, wp1, 64, 256)
-        elif self._x6_conv(n * hp1 * wp1, 256):
-            x1s, ax = self._split_act("x1s" if save else "x1se", p1, st1[2], st1[3], n, hp1, wp1, 64)
-            w2s, aw = self._split_w(P("visbl.conv2.weight"), 256 * 9, 64)
-            self._timed("conv_fwd", 2.0 * n * hp1 * wp1 * 576 * 256, ops.conv3x3_fwd_split, self._parts,
-                        x1s, w2s, P("visbl.conv2.bias"), True, y2, n, hp1, wp1, 64, 256, self._osc(ax, aw))
-            # conv2's weight gradient (3 output tiles of 256 x 256): 12.9 + 2.6 ms (split of dy2) against the fp32 kernel's 13.9 with six
-            # segments — no gain; with three (fp16x3) 6.5 + 3.3 against 14-20: taken
-            if save and self._parts == 2 and os.environ.get("GOALNET_X3_WGRAD2", "1") != "0":
-                ctx.update(x1s=x1s, x1s_amax=ax, x1s_gen=self._padgen["x1s"])
-            del x1s, w2s
-        else:
-            self._timed("conv_fwd", 2.0 * n * hp1 * wp1 * 576 * 256, ops.conv3x3_fwd,
-                        p1, st1[2], st1[3], P("visbl.conv2.weight"), P("visbl.conv2.bias"), True, y2, n, hp1, wp1, 64, 256)
-        p2, idx2, st2 = self._bn_block(y2, n, hp1, wp1, 256, 2, save, p16=p16_2)
-        del y2
+        b2, b3 = (hp1, wp1, 64, 256), (hp2, wp2, 256, 512)          # (hc, wc, cin, cout) of the two 3 x 3 blocks
+        # conv2's weight gradient (3 output tiles of 256 x 256): 12.9 + 2.6 ms (split of dy2) against the fp32 kernel's 13.9 with six
+        # segments — no gain; with three (fp16x3) 6.5 + 3.3 against 14-20: taken. conv3 keeps its split operands in both modes.
+        p2, idx2, st2, xh1 = self._conv_block_fwd(
+            2, p1, st1, n, *b2, save, ctx, p16=bf and self.act_bf16 and self._p16_ok(wp1, 256),
+            keep_split=self._parts == 2 and os.environ.get("GOALNET_X3_WGRAD2", "1") != "0")
         # <= 16 rows: linear5 is a pure weight stream; the fp32 weight-streaming kernels (csrc/skinny.hip) read the
         # arena once, which is cheaper (and exact) compared with casting 4 K J bytes to bf16 first
         bf5 = bf and (n > 16 or os.environ.get("GOALNET_FORCE_BF5") == "1")
-        p16_3 = bf5 and self.act_bf16 and self._p16_ok(wp2, 512)
-        y16_3 = p16_3 and ops.conv3x3_fwd_bf16p_o16_ok(n, hp2, wp2, 256, 512)
-        y3 = torch.empty(n, hp2, wp2, 512, dtype=BF16 if y16_3 else F32, device=dev)
-        if bf:
-            xh2 = ops.to_bf16_padded(p2, st2[2], st2[3], self._padbuf("x2" if save else "x2e", n, hp2, wp2, 256), n, hp2, wp2, 256)
-            w3b = ops.cast_bf16(P("visbl.conv3.weight"), torch.empty(512 * 9 * 256, dtype=BF16, device=dev))
-            self._timed("conv_fwd", 2.0 * n * hp2 * wp2 * 2304 * 512, ops.conv3x3_fwd_bf16p_o16 if y16_3 else ops.conv3x3_fwd_bf16p,
-                        xh2, w3b, P("visbl.conv3.bias"), True, y3, n, hp2, wp2, 256, 512)
-        elif self._x6_conv(n * hp2 * wp2, 256):
-            x2s, ax = self._split_act("x2s" if save else "x2se", p2, st2[2], st2[3], n, hp2, wp2, 256)
-            w3s, aw = self._split_w(P("visbl.conv3.weight"), 512 * 9, 256)
-            self._timed("conv_fwd", 2.0 * n * hp2 * wp2 * 2304 * 512, ops.conv3x3_fwd_split, self._parts,
-                        x2s, w3s, P("visbl.conv3.bias"), True, y3, n, hp2, wp2, 256, 512, self._osc(ax, aw))
-            if save:
-                ctx.update(x2s=x2s, x2s_amax=ax, x2s_gen=self._padgen["x2s"])
-            del x2s, w3s
-        else:
-            self._timed("conv_fwd", 2.0 * n * hp2 * wp2 * 2304 * 512, ops.conv3x3_fwd,
-                        p2, st2[2], st2[3], P("visbl.conv3.weight"), P("visbl.conv3.bias"), True, y3, n, hp2, wp2, 256, 512)
-        p3, idx3, st3 = self._bn_block(y3, n, hp2, wp2, 512, 3, save, p16=p16_3)
-        del y3
+        # p3 is linear5's operand: 16-bit only where linear5 runs its 16-bit kernels (bf5), i.e. fp32 for n <= 16
+        p3, idx3, st3, xh2 = self._conv_block_fwd(
+            3, p2, st2, n, *b3, save, ctx, p16=bf5 and self.act_bf16 and self._p16_ok(wp2, 512), keep_split=True)
 
         k5 = 512 * hp3 * wp3
         if self.grad_sync is not None:
@@ -804,13 +800,11 @@ class AVM(nn.Module):
                            dropmask=masks[1 + li], mult_out=m)
             hs.append(hnext); ms.append(m)
             x = hnext
-        if fused_mlp:
-            pass
-        elif self.head == "classifier":
+        if self.head == "classifier":                    # never fused: _mlp_fused serves the regression head only
             logit = torch.empty(n, self.num_classes, dtype=F32, device=dev)
             out = torch.empty(n, self.num_classes, dtype=F32, device=dev)          # class scores 4 softmax(z) + 1
             ops.cls_head_fwd(x, P("fusion.12.weight"), P("fusion.12.bias"), logit, out)
-        else:
+        elif not fused_mlp:
             logit = torch.empty(n, dtype=F32, device=dev)
             out = torch.empty(n, dtype=F32, device=dev)
             ops.head_fwd(x, P("fusion.12.weight"), P("fusion.12.bias"), logit, out)
@@ -885,6 +879,60 @@ class AVM(nn.Module):
         else:
             self._fork.run(lambda: ops.partials_sum(dparts, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias")), dparts)
         return dy
+
+    def _conv_block_bwd(self, i, dbn, ctx, n, hc, wc, cin, cout, wt, flipped, wait_ev, pair, out16, split_dgrad, after_block=None):
+        """Backward of block i (2 or 3): from dbn = grad wrt its BatchNorm output (N,hc-2,wc-2,cout) to the grad wrt block i-1's
+        BatchNorm output (N,hc,wc,cin), returned. _block_bwd, then conv{i}'s weight gradient (side stream, into the arena) and data
+        gradient on the engine its forward ran on (_conv_block_fwd).
+        wt: buffer for the flipped weight (csrc/layout.hip); flipped: the joint early launch fills it, and wait_ev is that launch's
+        event where this block is its first reader. pair: the weight gradient goes out behind the data gradient (backward_device).
+        out16: the data gradient may be stored in 16 bits; split_dgrad: it runs on split operands where the forward saved them;
+        after_block(): called between _block_bwd and the weight gradient."""
+        dev, P, G, fork = self._device, self._pflat, self._gflat, self._fork
+        wname, xs = f"visbl.conv{i}.weight", f"x{i - 1}s"
+        flops = 2.0 * n * hc * wc * 9 * cin * cout           # the same for the weight gradient and the data gradient
+        dy = self._block_bwd(dbn, ctx, i, n, hc, wc, cout)
+        if after_block:
+            after_block()
+        split = not self._half and xs in ctx           # the forward ran this convolution on split operands and kept them
+        if self._half:
+            wg, keep = (ops.conv3x3_wgrad_bf16, ctx[f"xh{i - 1}"], dy, G(wname), n, hc, wc, cin, cout), (dy,)
+        elif split:
+            if ctx[xs + "_gen"] != self._padgen[xs]:
+                raise RuntimeError(f"precision='{self.precision}': a second training-mode forward overwrote the saved split operands "
+                                   "before backward ran; call backward after each forward (as the reference's loop does)")
+            # the weight gradient and the data gradient read the gradient as 16-bit parts in the padded layout: one split pass
+            dys, ady = self._split_act(f"dy{i}s", dy, None, None, n, hc, wc, cout)
+            osc_w = self._osc(ady, ctx[xs + "_amax"])
+            # osc_w is kept too: the side stream reads it
+            wg, keep = (ops.conv3x3_wgrad_split, self._parts, ctx[xs], dys, G(wname), n, hc, wc, cin, cout, osc_w), (dys, osc_w)
+        else:
+            st_in = ctx[f"st{i - 1}"]
+            wg, keep = (ops.conv3x3_wgrad, ctx[f"p{i - 1}"], st_in[2], st_in[3], dy, G(wname), n, hc, wc, cin, cout), (dy,)
+
+        def wgrad():
+            fork.run(lambda: self._timed("conv_wgrad", flops, *wg), *keep)
+        if not pair:
+            wgrad()
+        if flipped:
+            fork.wait(wait_ev)                       # None: an earlier block's wait covered the joint flip launch
+        else:
+            ops.conv3x3_weight_flip(P(wname), wt, cout, cin)
+        o16 = out16 and ops.conv3x3_fwd_bf16p_o16_ok(n, hc, wc, cout, cin)
+        dx = torch.empty(n, hc, wc, cin, dtype=self._h16 if o16 else F32, device=dev)
+        if self._half:
+            wtb = ops.cast_bf16(wt, torch.empty(wt.shape, dtype=self._h16, device=dev))
+            self._timed("conv_dgrad", flops, ops.conv3x3_fwd_bf16p_o16 if o16 else ops.conv3x3_fwd_bf16p,
+                        dy, wtb, None, False, dx, n, hc, wc, cout, cin)
+        elif split and split_dgrad:
+            wts, awt = self._split_w(wt, cin * 9, cout)
+            self._timed("conv_dgrad", flops, ops.conv3x3_fwd_split, self._parts,
+                        dys, wts, None, False, dx, n, hc, wc, cout, cin, self._osc(ady, awt))
+        else:
+            self._timed("conv_dgrad", flops, ops.conv3x3_fwd, dy, None, None, wt, None, False, dx, n, hc, wc, cout, cin)
+        if pair:
+            wgrad()                                  # behind the data gradient: runs under the next block's BatchNorm / pool passes
+        return dx
 
     def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None):
         """dout (N,) GPU. Fills the gradient arena (every slot is overwritten). `on_bucket(k)` is called when
@@ -1008,100 +1056,18 @@ class AVM(nn.Module):
             if after_linear5:
                 deferred_l5.append(after_linear5) if pair else after_linear5(fork)
 
-        # block 3 (utils.py:184-187)
-        dy3 = self._block_bwd(dbn3, ctx, 3, n, hp2, wp2, 512)
+        b2, b3 = (hp1, wp1, 64, 256), (hp2, wp2, 256, 512)          # (hc, wc, cin, cout) of the two 3 x 3 blocks
+        # block 3 (utils.py:184-187): the first reader of the flipped weights (waits for the joint early launch). Its data gradient
+        # is kept in 16 bits where BLOCK 2's fused backward reads that (_bwd16_ok of block 2's width). pair: linear5's Adam starts
+        # behind _block_bwd, beside conv3's data gradient
+        dbn2 = self._conv_block_bwd(3, dbn3, ctx, n, *b3, wt3, flips_early, flips_ev, pair, out16=dz16 and self._bwd16_ok(wp1),
+                                    split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5])
         del dbn3
-        for cb in deferred_l5:                       # pair: linear5's Adam starts here, beside conv3's data gradient
-            cb(fork)
-        st2 = ctx["st2"]
-        x6_3 = "x2s" in ctx                          # precision="bf16x6" and the forward ran conv3 on split operands
-        if bf:
-            dyp3 = dy3
-            wg3 = lambda dyp3=dyp3: fork.run(lambda: self._timed("conv_wgrad", 2.0 * n * hp2 * wp2 * 2304 * 512, ops.conv3x3_wgrad_bf16,
-                                                                 ctx["xh2"], dyp3, G("visbl.conv3.weight"), n, hp2, wp2, 256, 512), dyp3)
-        elif x6_3:
-            if ctx["x2s_gen"] != self._padgen["x2s"]:
-                raise RuntimeError("precision='bf16x6': a second training-mode forward overwrote the saved split operands before "
-                                   "backward ran; call backward after each forward (as the reference's loop does)")
-            # the weight gradient and the data gradient read the gradient as 16-bit parts in the padded layout: one split pass
-            dys3, ady = self._split_act("dy3s", dy3, None, None, n, hp2, wp2, 512)
-            osc_w = self._osc(ady, ctx["x2s_amax"])
-            wg3 = lambda dys3=dys3, osc_w=osc_w: fork.run(
-                lambda: self._timed("conv_wgrad", 2.0 * n * hp2 * wp2 * 2304 * 512, ops.conv3x3_wgrad_split, self._parts,
-                                    ctx["x2s"], dys3, G("visbl.conv3.weight"), n, hp2, wp2, 256, 512, osc_w), dys3, osc_w)
-        else:
-            wg3 = lambda dy3=dy3: fork.run(lambda: self._timed("conv_wgrad", 2.0 * n * hp2 * wp2 * 2304 * 512, ops.conv3x3_wgrad,
-                                                               ctx["p2"], st2[2], st2[3], dy3, G("visbl.conv3.weight"), n, hp2, wp2, 256, 512), dy3)
-        if not pair:
-            wg3()
-        wt = wt3
-        if flips_early:
-            fork.wait(flips_ev)
-        else:
-            ops.conv3x3_weight_flip(P("visbl.conv3.weight"), wt, 512, 256)
-        o16_2 = dz16 and self._bwd16_ok(wp1) and ops.conv3x3_fwd_bf16p_o16_ok(n, hp2, wp2, 512, 256)
-        dbn2 = torch.empty(n, hp2, wp2, 256, dtype=self._h16 if o16_2 else F32, device=dev)
-        if self._half:
-            wtb = ops.cast_bf16(wt, torch.empty(wt.shape, dtype=self._h16, device=dev))
-            if o16_2:
-                self._timed("conv_dgrad", 2.0 * n * hp2 * wp2 * 4608 * 256, ops.conv3x3_fwd_bf16p_o16,
-                            dyp3, wtb, None, False, dbn2, n, hp2, wp2, 512, 256)
-            else:
-                self._timed("conv_dgrad", 2.0 * n * hp2 * wp2 * 4608 * 256, ops.conv3x3_fwd_bf16p,
-                            dyp3, wtb, None, False, dbn2, n, hp2, wp2, 512, 256)
-        elif x6_3:
-            wts, awt = self._split_w(wt, 256 * 9, 512)
-            self._timed("conv_dgrad", 2.0 * n * hp2 * wp2 * 4608 * 256, ops.conv3x3_fwd_split, self._parts,
-                        dys3, wts, None, False, dbn2, n, hp2, wp2, 512, 256, self._osc(ady, awt))
-            del dys3, wts
-        else:
-            self._timed("conv_dgrad", 2.0 * n * hp2 * wp2 * 4608 * 256, ops.conv3x3_fwd,
-                        dy3, None, None, wt, None, False, dbn2, n, hp2, wp2, 512, 256)
-        if pair:
-            wg3()                                    # behind the data gradient: runs under block 2's BatchNorm / pool passes
-        del dy3
-
-        # block 2 (utils.py:179-182)
-        dy2 = self._block_bwd(dbn2, ctx, 2, n, hp1, wp1, 256)
+        # block 2 (utils.py:179-182): no wait (conv3's covered the joint flip launch); dbn1 is always fp32, its consumer is block 1's
+        # fp32 path; fp16x3: the split gradient is there already (weight gradient) -> 128 x 64 tile, three segments
+        dbn1 = self._conv_block_bwd(2, dbn2, ctx, n, *b2, wt2, flips_early, None, pair, out16=False,
+                                    split_dgrad=os.environ.get("GOALNET_X3_DGRAD2", "1") != "0")
         del dbn2
-        st1 = ctx["st1"]
-        if bf:
-            dyp2 = dy2
-            wg2 = lambda dyp2=dyp2: fork.run(lambda: self._timed("conv_wgrad", 2.0 * n * hp1 * wp1 * 576 * 256, ops.conv3x3_wgrad_bf16,
-                                                                 ctx["xh1"], dyp2, G("visbl.conv2.weight"), n, hp1, wp1, 64, 256), dyp2)
-        elif "x1s" in ctx:
-            if ctx["x1s_gen"] != self._padgen["x1s"]:
-                raise RuntimeError("precision='fp16x3': a second training-mode forward overwrote the saved split operands before backward ran")
-            dys2, ady2 = self._split_act("dy2s", dy2, None, None, n, hp1, wp1, 256)
-            osc_w2 = self._osc(ady2, ctx["x1s_amax"])
-            wg2 = lambda dys2=dys2, osc_w2=osc_w2: fork.run(
-                lambda: self._timed("conv_wgrad", 2.0 * n * hp1 * wp1 * 576 * 256, ops.conv3x3_wgrad_split, self._parts,
-                                    ctx["x1s"], dys2, G("visbl.conv2.weight"), n, hp1, wp1, 64, 256, osc_w2), dys2, osc_w2)
-        else:
-            wg2 = lambda dy2=dy2: fork.run(lambda: self._timed("conv_wgrad", 2.0 * n * hp1 * wp1 * 576 * 256, ops.conv3x3_wgrad,
-                                                               ctx["p1"], st1[2], st1[3], dy2, G("visbl.conv2.weight"), n, hp1, wp1, 64, 256), dy2)
-        if not pair:
-            wg2()
-        wt = wt2
-        if not flips_early:
-            ops.conv3x3_weight_flip(P("visbl.conv2.weight"), wt, 256, 64)
-        dbn1 = torch.empty(n, hp1, wp1, 64, dtype=F32, device=dev)
-        if self._half:
-            wtb = ops.cast_bf16(wt, torch.empty(wt.shape, dtype=self._h16, device=dev))
-            self._timed("conv_dgrad", 2.0 * n * hp1 * wp1 * 2304 * 64, ops.conv3x3_fwd_bf16p,
-                        dyp2, wtb, None, False, dbn1, n, hp1, wp1, 256, 64)
-        elif "x1s" in ctx and os.environ.get("GOALNET_X3_DGRAD2", "1") != "0":
-            # fp16x3: the split gradient is there already (weight gradient above); 128 x 64 tile, three segments
-            wts2, awt2 = self._split_w(wt, 64 * 9, 256)
-            self._timed("conv_dgrad", 2.0 * n * hp1 * wp1 * 2304 * 64, ops.conv3x3_fwd_split, self._parts,
-                        dys2, wts2, None, False, dbn1, n, hp1, wp1, 256, 64, self._osc(ady2, awt2))
-            del wts2
-        else:
-            self._timed("conv_dgrad", 2.0 * n * hp1 * wp1 * 2304 * 64, ops.conv3x3_fwd,
-                        dy2, None, None, wt, None, False, dbn1, n, hp1, wp1, 256, 64)
-        if pair:
-            wg2()
-        del dy2
 
         # block 1 (utils.py:174-177); conv1's input needs no gradient
         dy1 = self._block_bwd(dbn1, ctx, 1, n, h1, w1, 64)

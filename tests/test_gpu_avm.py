@@ -483,3 +483,21 @@ def test_bf16_mode_on_frames_wider_than_the_fused_backward_serves():
         mine = model.grad_of(k).cpu().reshape(og.shape)
         l2 = ((mine - og).norm() / og.norm().clamp_min(1e-30)).item()
         assert l2 <= 0.15, f"{k}: relative L2 error {l2:.3f}"
+
+
+@pytest.mark.parametrize("precision", ["bf16x6", "fp16x3"])
+def test_backward_refuses_split_operands_a_second_forward_overwrote(precision):
+    """precision="bf16x6" / "fp16x3" at 13 frames of 224 x 224, the fewest at which conv2 and conv3 both run on split operands:
+    backward reads the split activations the forward left in the cached padded buffers. A second training-mode forward
+    overwrites them; the backward of the first must raise, naming the model's precision, instead of using the wrong operands."""
+    n, h = 13, 224
+    torch.manual_seed(5)
+    model = AVM(audio_included=True, device=DEV, precision=precision, seed=synth.BASE_SEED)
+    vis = torch.from_numpy(synth.make_visual(n, h, h)).to(DEV)
+    aud = torch.from_numpy(synth.make_audio(n)).to(DEV)
+    _, ctx = model.forward_device(aud, vis, save=True)
+    assert "x2s" in ctx, "conv3 did not run on split operands: the test would be vacuous"
+    model.forward_device(aud, vis, save=True)
+    with pytest.raises(RuntimeError, match=f"precision='{precision}'.*overwrote the saved split operands"):
+        model.backward_device(ctx, torch.ones(n, device=DEV))
+    torch.cuda.synchronize()

@@ -10,7 +10,7 @@ step at that resolution, so a 1 024-frame oracle step is out of reach; two const
   variance factor M/(M-1) recomputed for the larger pixel count) of the N = 1 024 step, while the device runs every
   > 2^31-element index path, the 256 x 256 tiles, split-K slab counts and grid sizes of the timed configuration.
 * **n = 32 at 224 x 224 and at 40 x 40** (precision="bf16"): n > 16 is where `AVM.forward_device` switches linear5, p3, y3 and
-  the BatchNorm-3 output gradient to their bf16 forms (`bf5 / p16_3 / y16_3 / o16_3`); forward and backward are compared
+  the BatchNorm-3 output gradient to their bf16 forms (`bf5`, block 3's `p16` / `y16`, `o16_3`); forward and backward are compared
   with the oracle under the device's max-pool routing.
 
 Both max-pool routing and the ReLU gate at the routed position are discontinuous in the convolution's output; the backward
@@ -296,7 +296,7 @@ def test_fp16_step_of_2048_frames_of_224_as_128_copies():
 
 @pytest.mark.parametrize("h,precision", [(224, "bf16"), (40, "bf16"), (40, "fp16")])
 def test_16bit_step_of_32_frames_forward_and_backward_vs_oracle(h, precision):
-    """n > 16: linear5 / p3 / y3 / dbn3 on their 16-bit forms (avm.py forward_device: bf5, p16_3, y16_3; backward: o16_3).
+    """n > 16: linear5 / p3 / y3 / dbn3 on their 16-bit forms (avm.py forward_device: bf5, block 3's p16 / y16 in _conv_block_fwd; backward: o16_3).
     fp16 at 224 x 224 runs the same branches in the 2 048-frame test above and at 16 frames in tests/test_gpu_fp16.py."""
     _run_case(precision, h, 32, 1)
 

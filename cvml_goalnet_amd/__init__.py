@@ -4,6 +4,7 @@ surface. See DESIGN.md / INTEGRATION.md.
 
     from cvml_goalnet_amd import AVM               # drop-in for /root/reference/utils.py:229 `AVM`
     from cvml_goalnet_amd import VideoSummarizer   # /root/reference/main.py:315-345 (`--infer`) on a video resident on the GPU
+    from cvml_goalnet_amd import TemporalSegmenter # KTS change points for a video outside the dataset (extension, parity unpinned)
 """
 from . import synth  # noqa: F401
 from ._lib import GoalnetError, LIB_PATH  # noqa: F401
@@ -11,5 +12,7 @@ from .avm import AVM  # noqa: F401
 from . import optim  # noqa: F401
 from .summarize import VideoSummarizer, VideoSummary  # noqa: F401
 from . import groundtruth  # noqa: F401
+from .segment import Segmentation, TemporalSegmenter  # noqa: F401
 
-__all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "VideoSummarizer", "VideoSummary", "groundtruth"]
+__all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
+           "Segmentation"]

@@ -812,6 +812,7 @@ class AVM(nn.Module):
             ctx.update(p1=p1, idx1=idx1, st1=st1, p2=p2, idx2=idx2, st2=st2, p3=p3, idx3=idx3, st3=st3,
                        a1=a1, a2=a2, hs=hs, ms=ms, logit=logit, out=out, l1=l1, l2=l2)
         self.last_logit = logit
+        self.last_features = cat                    # the fusion input (N, 512 | 640): what TemporalSegmenter segments (no copy)
         return out, ctx
 
     def _block_bwd(self, dbn, ctx, i, n, hc, wc, c):

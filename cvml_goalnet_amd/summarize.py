@@ -17,7 +17,7 @@ No CPU fallback: without the library / a GPU the call raises.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -33,6 +33,7 @@ class VideoSummary:
     selected: List[int]            # indices of the selected clips (rows of change_points)
     src_index: torch.Tensor        # (count,) int32 on the device: the source frame of every summary frame
     predictions: torch.Tensor      # (N, 1) float32 on the device: the model's importance of every sampled frame
+    change_points: Optional[np.ndarray] = None   # (n_clips, 2) int32: the change points the summary was made with
 
 
 class VideoSummarizer:
@@ -44,20 +45,31 @@ class VideoSummarizer:
     The model runs under `no_grad` IN ITS CURRENT MODE. The reference never calls `.eval()` (main.py:325-331), so there — and here
     with a model left in train mode — BatchNorm normalises with the statistics of the whole video and updates its running
     buffers, and dropout is active. Call `model.eval()` first for a summary that depends on the checkpoint alone; that is the
-    recommended use."""
+    recommended use.
 
-    def __init__(self, model, change_points, skip_frames: int = 60, size=(40, 40)):
+    A video outside the dataset has no change points to read: `VideoSummarizer(model, None, ..., segmenter=TemporalSegmenter())`
+    computes them per video (cvml_goalnet_amd/segment.py: KTS on the device — an extension, parity unpinned, no reference code)
+    from `model.last_features`, the fusion input of the very forward pass that gives the importances, builds the evaluator from them
+    and returns them as `VideoSummary.change_points`. `model.eval()` is recommended here all the more: in train mode dropout
+    perturbs the visual half of the descriptor, and with it the segmentation. This adds ONE host read-back per video (two in all),
+    because n_clips sizes the evaluator's buffers. With explicit change points the segmenter is not used and nothing changes."""
+
+    def __init__(self, model, change_points, skip_frames: int = 60, size=(40, 40), segmenter=None):
         if getattr(model, "head", "regression") != "regression":
             raise ValueError("VideoSummarizer needs the regression head: post-processing takes one importance per frame")
-        cps = np.asarray(change_points)
-        if cps.ndim != 2 or cps.shape[1] != 2 or cps.shape[0] < 1:
-            raise ValueError("change_points must be [n_clips][2]")
+        if change_points is None and segmenter is not None:
+            cps = None
+        else:
+            cps = np.asarray(change_points)
+            if cps.ndim != 2 or cps.shape[1] != 2 or cps.shape[0] < 1:
+                raise ValueError("change_points must be [n_clips][2] (or None together with a segmenter)")
         if int(skip_frames) < 1:
             raise ValueError("skip_frames must be positive")
         self.model = model
         self.change_points = cps
         self.skip_frames = int(skip_frames)
         self.size = (int(size[0]), int(size[1]))
+        self.segmenter = segmenter if cps is None else None
         self._evaluators = {}          # full_n -> SummaryEvaluator (change points and buffers stay resident between videos)
 
     def _evaluator(self, full_n: int) -> SummaryEvaluator:
@@ -100,6 +112,11 @@ class VideoSummarizer:
                     audio = extract_audio_features(waveform, n, int(bin_length), sr, dev)
             out, _ = model.forward_device(audio, visual, save=False)
             predictions = out.view(-1, 1)
-            ev = self._evaluator(full_n)
+            if self.segmenter is not None:
+                cps = self.segmenter.segment(model.last_features, full_n, self.skip_frames, dev).change_points
+                ev = SummaryEvaluator(cps, full_n, self.skip_frames, None, dev)       # this video's own clips: nothing to keep resident
+            else:
+                cps = self.change_points
+                ev = self._evaluator(full_n)
             frames, mask = ev.summarize(predictions, t)
-        return VideoSummary(frames, mask, ev.last_selected, ev.last_src_index, predictions)
+        return VideoSummary(frames, mask, ev.last_selected, ev.last_src_index, predictions, cps)

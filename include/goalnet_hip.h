@@ -494,6 +494,27 @@ int goalnet_gather_clips(const uint8_t* frames, int full_n, int64_t frame_bytes,
                          int n_clips, uint8_t* out, int64_t out_capacity_frames, int32_t* src_index, int64_t* count, int32_t* status,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the change points themselves: Kernel Temporal Segmentation (Potapov et al., ECCV 2014), linear kernel -----------------
+ * EXTENSION, PARITY UNPINNED (no reference code): the reference reads its change points from the dataset's HDF5 file
+ * (utils.py:424-431) and holds no segmentation code; the oracle is the project's restatement (tests/kts_ref.py).
+ * x: descriptors [n][d] float32, 1 <= n <= 8192, 1 <= d <= 4096 (the fusion input of the model, one row per sampled frame);
+ * normalize != 0: every row is divided by its L2 norm first (a row of zeros stays zero). All arithmetic in float64.
+ * Scatter of samples [i, j], L = j - i + 1: J = (D[j+1] - D[i]) - ||S[j+1] - S[i]||^2 / L from the prefix sums S (of the rows) and
+ * D (of their squared norms) when lmin <= L <= lmax, +inf otherwise; I[0][l] = J(0, l-1), I[k][l] = min over t in
+ * [k lmin, l - lmin] of I[k-1][t] + J(t, l-1), ties to the smallest t; m = the smallest minimiser of
+ * I[m][n] / n + (vmax m / (2n)) (ln(n / m) + 1) (0 for m = 0) among the finite ones, 0 <= m <= max_cp <= n - 1.
+ * Outputs (device): cost / objective [max_cp+1] for every m (+inf where no segmentation exists); n_clips [1] = m + 1;
+ * cps_samples [max_cp]: the m change points in samples, ascending, then -1; change_points [(max_cp+1)][2] int32 in frames, end
+ * inclusive as in the dataset file: clip r = [c_r skip_frames, c_(r+1) skip_frames - 1], c_0 = 0, the last clip ends at
+ * full_n_frames - 1, rows from n_clips on hold -1; status [1]: 0, or 1 = no feasible segmentation (lmin / lmax rule out every m;
+ * then n_clips = 0) — a data condition, not a return code. full_n_frames must give n = ceil(full_n_frames / skip_frames).
+ * ws: goalnet_kts_ws_bytes (0 for dims outside the limits), 16-byte aligned: S, D, the n x n scatter table (float64) and the
+ * (max_cp+1) x (n+1) tables I (float64) and P (int32). 4 + max_cp + 1 launches on `stream`, no allocation, no synchronisation. */
+size_t goalnet_kts_ws_bytes(int n, int d, int max_cp);
+int goalnet_kts(const float* x, int n, int d, int normalize, int max_cp, int lmin, int lmax, double vmax, int skip_frames,
+                int full_n_frames, int32_t* change_points, int32_t* n_clips, int32_t* cps_samples, double* cost, double* objective,
+                int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* up to GOALNET_ROWCOPY_MAX gathers (gather != 0: dst[0:nrows] = src[c : c + nrows]) and scatters
  * (gather == 0: dst[c : c + nrows] = src[0:nrows]) in one launch; c = *cursor + cursor_bias */
 #define GOALNET_ROWCOPY_MAX 4

@@ -13,6 +13,10 @@
 // products hi hi, hi mid, mid hi (the dropped mid mid is 2^-22 |a b|): half the MFMA work of bf16x6. The GEMM epilogues undo the two
 // scales with one ldexpf (EpiP::oscale = the exponent from goalnet_split_scales: exact, no intermediate that could overflow); a bias is
 // added after that, not carried in the accumulators.
+// Dynamic range of fp16x3: the scale is per TENSOR. An element 2^r below the tensor's largest magnitude keeps its 22 bits while `mid` is a
+// normal binary16 (r <= 17), has relative error 2^(r - 39) beyond (mid, then hi, in binary16's subnormals) and is exactly zero from r = 40.
+// An output row fed only by such values (a near-dead channel of dy, a frame with a tiny gradient) meets the 6e-6 criterion on its OWN
+// scale up to r = 20 (tests/test_split_rows_host.py; the kernels against that arithmetic: tests/test_gpu_ops.py). bf16x6 has no such limit.
 //
 // This file: the split passes (activations into the zero-padded layout with the BatchNorm affine applied, weights and linear5's
 // operands row by row), the magnitude pass of fp16x3 and the C-ABI entry points. fp32 everywhere else: results, accumulators, bias, ReLU.

@@ -90,15 +90,19 @@ def natural_taps(y: torch.Tensor):
     return taps, gap, pooled
 
 
-def _vis_block(x, p, b, i, stride, pad, inter, taps=None, gate=None):
+def _vis_block(x, p, b, i, stride, pad, inter, taps=None, gate=None, store=None):
     """conv -> ReLU -> MaxPool(3,1) -> train-mode BatchNorm  (utils.py:174-187).
+    store (tests only, see forward): applied to the weight, the convolution's output and the BatchNorm's output where they are stored.
     taps / gate (tests only): the max-pool's argmax positions and the ReLU's gate AT those positions are given. ReLU is as
     discontinuous as the max-pool's routing: a window maximum within rounding error of zero is passed by one correct fp32
     convolution (y = +1e-9: the gradient flows) and blocked by another (y = -1e-9), and that one element then shows up at
     O(1) in the bias / weight gradients of the layer. Parity tests compare backward passes under the device's decisions and
     check separately that every decision that differs from the oracle's own is such a near-zero (tests/test_gpu_bench_shapes.py)."""
     pre = f"visbl.conv{i}"
-    x = F.conv2d(x, p[pre + ".weight"], p[pre + ".bias"], stride=stride, padding=pad)
+    if store is None:
+        x = F.conv2d(x, p[pre + ".weight"], p[pre + ".bias"], stride=stride, padding=pad)
+    else:
+        x = store(pre, F.conv2d(x, store(pre + ".weight", p[pre + ".weight"]), p[pre + ".bias"], stride=stride, padding=pad))
     if inter is not None:
         inter[pre] = x                                        # pre-activation
     if taps is not None and gate is not None:
@@ -116,6 +120,8 @@ def _vis_block(x, p, b, i, stride, pad, inter, taps=None, gate=None):
     x = F.batch_norm(x, b[bn + ".running_mean"], b[bn + ".running_var"], p[bn + ".weight"], p[bn + ".bias"],
                      training=True, momentum=BN_MOMENTUM, eps=BN_EPS)
     b[bn + ".num_batches_tracked"] += 1
+    if store is not None:
+        x = store(bn, x)
     if inter is not None:
         inter[bn] = x
     return x
@@ -124,7 +130,7 @@ def _vis_block(x, p, b, i, stride, pad, inter, taps=None, gate=None):
 def forward(p: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], audio, visual,
             drop_masks: Optional[List[torch.Tensor]] = None, audio_included: bool = True,
             inter: Optional[dict] = None, pool_taps: Optional[dict] = None, head: str = "regression",
-            relu_gates: Optional[dict] = None) -> torch.Tensor:
+            relu_gates: Optional[dict] = None, store=None) -> torch.Tensor:
     """AVM.forward(audio_input, visual_input) -> (N,1) in (1,5).  utils.py:260-272.
 
     `b` (BN running stats) is updated in place, as the reference's train-mode forward does even under
@@ -135,6 +141,10 @@ def forward(p: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], audio, visua
     pool_taps: whether the ReLU passes at each forced argmax position (tests only, see _vis_block); optional keys "visbl.linear5",
     "fusion.0" / ".3" / ".6" / ".9" -> bool (N, width): the gate of that layer's ReLU (tests of the 16-bit modes, whose 4e-3
     activation noise flips ~0.5 % of a ReLU network's gates: the gradient's relative error is then ~sqrt(0.5 %), whatever the kernels do).
+    `store`: optional callable (name, tensor) -> tensor applied where a 16-bit mode of the device STORES a tensor (tests only: the emulation of
+    16-bit storage that tests/_decisions.py measures its activation noise with): "visbl.conv{i}" (the convolution's output),
+    "visbl.bnorm{i}" (the BatchNorm's output = the next GEMM's operand), "visbl.conv{i}.weight" / "visbl.linear5.weight" (GEMM operands).
+    None = the reference's own arithmetic, untouched.
     """
     pt = pool_taps or {}
     rg = relu_gates or {}
@@ -144,16 +154,19 @@ def forward(p: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], audio, visua
         return x if m is None else x * m
 
     # VisBl, utils.py:172-195
-    x = _vis_block(visual, p, b, 1, 3, 3, inter, pt.get(1), rg.get(1))
-    x = _vis_block(x, p, b, 2, 1, 1, inter, pt.get(2), rg.get(2))
-    x = _vis_block(x, p, b, 3, 1, 1, inter, pt.get(3), rg.get(3))
+    x = _vis_block(visual, p, b, 1, 3, 3, inter, pt.get(1), rg.get(1), store)
+    x = _vis_block(x, p, b, 2, 1, 1, inter, pt.get(2), rg.get(2), store)
+    x = _vis_block(x, p, b, 3, 1, 1, inter, pt.get(3), rg.get(3), store)
     def relu_g(z, key):
         """ReLU, or (tests) the given gate at this layer: z * gate — see _vis_block on why gates are forced"""
+        if inter is not None:
+            inter[key] = z                                    # pre-activation
         g = rg.get(key)
         return F.relu(z) if g is None else z * g.to(z.dtype)
 
     x = torch.flatten(x, 1)                                   # NCHW flatten: c*H*W + h*W + w
-    x = relu_g(F.linear(x, p["visbl.linear5.weight"], p["visbl.linear5.bias"]), "visbl.linear5")
+    w5 = p["visbl.linear5.weight"] if store is None else store("visbl.linear5.weight", p["visbl.linear5.weight"])
+    x = relu_g(F.linear(x, w5, p["visbl.linear5.bias"]), "visbl.linear5")
     v = drop(x, dm[0])
     if inter is not None:
         inter["visbl.drop5"] = v

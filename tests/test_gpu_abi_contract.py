@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from _abi_guard import Bands, bits_equal, ptr
+from _decisions import saved_mult_check
 from cvml_goalnet_amd import _lib, synth
 from oracle import avm_ref
 from test_gpu_ops import _scale_of, _split_host, close, nchw, nhwc, rnd
@@ -870,7 +871,8 @@ def test_linear_fwd_bf16_guarded(m, k, j, tile, fmt, monkeypatch):
     dt, f16 = H16[fmt], int(fmt == "fp16")
     x, w, b = rnd(m, k, seed=56).to(dt), rnd(j, k, seed=57, lo=-0.05, hi=0.05).to(dt), rnd(j, seed=58)
     dm = (torch.rand(m, j, generator=torch.Generator().manual_seed(59)) >= 0.2).float() * 1.25
-    ref = F.relu(x.double() @ w.double().t() + b.double()) * dm.double()
+    pre = x.double() @ w.double().t() + b.double()
+    ref = F.relu(pre) * dm.double()
     bands = Bands()
     xg, wg, bg, dmg = bands.place_rows(x, k + 8, "x"), bands.place(w, "w"), bands.place(b, "bias"), bands.place_rows(dm, j + 4, "dropmask")
     y, mult = bands.guarded_rows(m, j, j + 4, F32, name="y"), bands.guarded_rows(m, j, j + 8, F32, name="mult_out")
@@ -879,7 +881,7 @@ def test_linear_fwd_bf16_guarded(m, k, j, tile, fmt, monkeypatch):
     _ok(lib.goalnet_linear_fwd_bf16(ptr(xg), k + 8, ptr(wg), ptr(bg), 1, ptr(dmg), j + 4, ptr(y), j + 4, ptr(mult), j + 8, m, k, j, ptr(ws), nbytes, f16, _s()),
         "linear_fwd_bf16")
     close(f"linear_fwd_bf16[{m}x{k}->{j}] {tile} {fmt}", y, ref, rtol=3e-6)
-    assert torch.isfinite(mult).all()
+    saved_mult_check(f"linear_fwd_bf16[{m}x{k}->{j}] {tile} {fmt}", mult, pre, dm, 3e-6)
     bands.assert_bands_intact()
 
 
@@ -1002,7 +1004,8 @@ def _split_linear_case():
         sc, sh = rnd(bnc, seed=321, lo=0.5, hi=1.5), rnd(bnc, seed=322, lo=-0.5, hi=0.5)
         mask = (rnd(m, j, seed=326) > 0).float() * 2.0
         xh = x.double() * sc.double().repeat(k // bnc) + sh.double().repeat(k // bnc)
-        _SPLIT_LINEAR_CASE.append((x, w, b, sc, sh, mask, F.relu(xh @ w.double().t() + b.double()) * mask.double()))
+        pre = xh @ w.double().t() + b.double()
+        _SPLIT_LINEAR_CASE.append((x, w, b, sc, sh, mask, F.relu(pre) * mask.double(), pre))
     return _SPLIT_LINEAR_CASE[0]
 
 
@@ -1013,7 +1016,7 @@ def test_linear_fwd_split_guarded(parts):
     m, k, j, bnc = SPLIT_LINEAR
     assert lib.goalnet_linear_split_ok(parts, m, k, j)
     dt = torch.bfloat16 if parts == 3 else torch.float16
-    x, w, b, sc, sh, mask, ref = _split_linear_case()
+    x, w, b, sc, sh, mask, ref, pre = _split_linear_case()
     bands = Bands()
     xg, wg, bg, scg, shg, mg = (bands.place(t, nm) for t, nm in ((x, "x"), (w, "w"), (b, "bias"), (sc, "scale"), (sh, "shift"), (mask, "dropmask")))
     ax = aw = osc = None
@@ -1029,7 +1032,7 @@ def test_linear_fwd_split_guarded(parts):
     _ok(lib.goalnet_linear_fwd_split(parts, ptr(xs), ptr(wsp), ptr(bg), 1, ptr(mg), j, ptr(y), j + 4, ptr(mult), j + 8, m, k, j, ptr(ws), nbytes, ptr(osc), _s()),
         "linear_fwd_split")
     close(f"linear_fwd_split[{parts}] vs fp64", y, ref, rtol=6e-6)
-    assert torch.isfinite(mult).all()
+    saved_mult_check(f"linear_fwd_split[{parts}]", mult, pre, mask, 6e-6)
     bands.assert_bands_intact()
 
 

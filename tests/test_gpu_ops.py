@@ -8,6 +8,8 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from _decisions import saved_mult_check  # noqa: E402
+from _split_emul import check_rows, ideal_split_product, rows_at_exponents, split_host as _split_host  # noqa: E402
 from cvml_goalnet_amd import ops, synth  # noqa: E402
 from oracle import avm_ref  # noqa: E402
 
@@ -403,16 +405,36 @@ def test_conv3x3_fwd_bf16(n, h, w, cin, cout, bias, relu):
 @pytest.mark.parametrize("tile", ["128", "256"])
 @pytest.mark.parametrize("m,k,j", [(10, 41472, 512), (37, 640, 512), (130, 512, 256), (300, 8192, 320)])
 def test_linear_fwd_bf16(m, k, j, tile, monkeypatch):
+    """goalnet_linear_fwd_bf16 on bf16 and on fp16 operands, both tiles: y against fp64 on the exactly rounded operands (3e-6), and the
+    multiplier it saves for backward — written into a column slice of a wider buffer, as AVM's ms[0][:, voff:] is — bit for bit
+    (pre > 0) * dropmask wherever |pre| exceeds the error y is allowed (tests/_decisions.py::saved_mult_check). relu without a mask saves
+    the bare gate; without relu the epilogue's gate stays 1 (csrc/gemm_common.h: epi_apply), so the saved multiplier IS the dropout mask."""
     monkeypatch.setenv("GOALNET_BF16_TILE", tile)
-    x = rnd(m, k, seed=56).to(torch.bfloat16)
-    w = rnd(j, k, seed=57, lo=-0.05, hi=0.05).to(torch.bfloat16)
-    b = rnd(j, seed=58)
-    dm = (torch.rand(m, j, generator=torch.Generator().manual_seed(59)) >= 0.2).float() * 1.25
-    ref = F.relu(x.double() @ w.double().t() + b.double()) * dm.double()
-    y = torch.full((m, j), float("nan"), device=DEV)
-    mv = torch.empty(m, j, device=DEV)
-    ops.linear_fwd_bf16(x.to(DEV), w.to(DEV), b.to(DEV), y, relu=True, dropmask=dm.to(DEV), mult_out=mv)
-    close(f"linear_fwd_bf16[{m}x{k}->{j}]", y, ref, rtol=3e-6)
+    voff = 128
+    for dtype in (torch.bfloat16, torch.float16):
+        x = rnd(m, k, seed=56).to(dtype)
+        w = rnd(j, k, seed=57, lo=-0.05, hi=0.05).to(dtype)
+        b = rnd(j, seed=58)
+        dm = (torch.rand(m, j, generator=torch.Generator().manual_seed(59)) >= 0.2).float() * 1.25
+        pre = x.double() @ w.double().t() + b.double()
+        name = f"linear_fwd_bf16[{m}x{k}->{j}] {str(dtype)[6:]}"
+        xd, wd, bd, dmd = x.to(DEV), w.to(DEV), b.to(DEV), dm.to(DEV)
+        y = torch.full((m, j), float("nan"), device=DEV)
+        mbuf = torch.full((m, voff + j), float("nan"), device=DEV)
+        ops.linear_fwd_bf16(xd, wd, bd, y, relu=True, dropmask=dmd, mult_out=mbuf[:, voff:])
+        close(name, y, F.relu(pre) * dm.double(), rtol=3e-6)
+        saved_mult_check(name, mbuf[:, voff:], pre, dm, 3e-6)
+        assert torch.isnan(mbuf[:, :voff]).all(), "the saved multiplier was written outside its column slice"
+        mbuf.fill_(float("nan"))
+        ops.linear_fwd_bf16(xd, wd, bd, y.fill_(float("nan")), relu=True, dropmask=None, mult_out=mbuf[:, voff:])
+        close(name + " no mask", y, F.relu(pre), rtol=3e-6)
+        saved_mult_check(name + " no mask", mbuf[:, voff:], pre, None, 3e-6)
+        assert torch.isnan(mbuf[:, :voff]).all()
+        mbuf.fill_(float("nan"))
+        ops.linear_fwd_bf16(xd, wd, bd, y.fill_(float("nan")), relu=False, dropmask=dmd, mult_out=mbuf[:, voff:])
+        close(name + " no relu", y, pre * dm.double(), rtol=3e-6)
+        assert torch.equal(mbuf[:, voff:].cpu(), dm), "without ReLU the saved multiplier must be the dropout mask itself"
+        assert torch.isnan(mbuf[:, :voff]).all()
 
 
 def _padded(x_nhwc_f32, sc=None, sh=None):
@@ -779,16 +801,6 @@ def test_tile_walk_of_the_256_kernel_equals_one_block_per_tile_bit_for_bit():
 # ------------------------------------------------------------------------------------------------
 # precision = "bf16x6" / "fp16x3" (csrc/split3.hip): fp32 operands as bf16 triples (six partial products per product) or as fp16 pairs of
 # the power-of-two-scaled value (three partial products) on the 16-bit MFMA
-def _split_host(x, parts, s=1.0):
-    """the parts computed by torch on the host (round to nearest even): bf16 (hi, mid, lo) of x, or fp16 (hi, mid) of x * s"""
-    dt = torch.bfloat16 if parts == 3 else torch.float16
-    v = x * s
-    hi = v.to(dt)
-    r1 = v - hi.float()
-    mid = r1.to(dt)
-    return (hi, mid, (r1 - mid.float()).to(dt)) if parts == 3 else (hi, mid)
-
-
 def _amax_word(x2d, rows, c, scale=None, shift=None, bnC=0):
     return ops.absmax(x2d, torch.zeros(1, dtype=torch.int32, device=DEV), rows, c, scale=scale, shift=shift, bnC=bnC)
 
@@ -899,7 +911,8 @@ def test_conv3x3_split_forward_data_gradient_and_weight_gradient_vs_fp64(n, h, w
 def test_linear5_on_split_operands_forward_dx_dw_vs_fp64(parts):
     """goalnet_linear_fwd_split / _bwd_dx_split / _bwd_dw_split (linear5's three contractions under precision="bf16x6" / "fp16x3") against
     fp64 on the unrounded fp32 operands: ragged in M (320 = 256 + 64) and K (a partial last 256-column tile), BatchNorm affine applied on
-    the way into the split, bias + ReLU + dropout mask + saved multiplier in the forward's reduction epilogue. fp32-grade: 6e-6 of the scale."""
+    the way into the split, bias + ReLU + dropout mask + saved multiplier in the forward's reduction epilogue. fp32-grade: 6e-6 of the scale;
+    the saved multiplier is exact away from z = 0 (tests/_decisions.py::saved_mult_check)."""
     dt = torch.bfloat16 if parts == 3 else torch.float16
     m, k, j, bnc = 320, 66048 + 64, 256, 64
     assert ops.linear_split_ok(parts, m, k, j) and not ops.linear_split_ok(parts, 10, k, j)
@@ -922,7 +935,8 @@ def test_linear5_on_split_operands_forward_dx_dw_vs_fp64(parts):
     xh = x.double() * sc.double().repeat(k // bnc) + sh.double().repeat(k // bnc)
     z = xh @ w.double().t() + b.double()
     close(f"linear_fwd_split[{parts}] vs fp64", y, F.relu(z) * mask.double(), rtol=6e-6)
-    assert torch.isfinite(mult).all()
+    # the multiplier saved for backward: (z > 0) * mask bit for bit outside 6e-6 of max|z|, this test's own tolerance
+    saved_mult_check(f"linear_fwd_split[{parts}]", mult, z, mask, 6e-6)
     dyd = torch.zeros(m, j + 128, device=DEV)
     dyd[:, 128:] = dy.to(DEV)
     ady = _amax_word(dyd[:, 128:], m, j) if parts == 2 else None
@@ -960,3 +974,87 @@ def test_fp16x3_scaling_keeps_any_fp32_magnitude_in_range(magnitude):
         assert not y.any()
     else:
         close(f"conv of x * {magnitude:g} on scaled fp16 pairs vs fp64", y, ref, rtol=6e-6)
+
+
+# ------------------------------------------------------------------------------------------------
+# per-row accuracy of the split-operand GEMMs over mixed magnitudes: `close()` divides by the TENSOR's maximum and says nothing about an
+# output row fed only by small operand values (a near-dead channel of dy, a frame with a tiny gradient). Here one operand has its rows at
+# 2^-r of the tensor's maximum, r in tests/_split_emul.py::ROW_EXPONENTS, along the axis the contraction does NOT mix, and every output
+# row is judged on its own scale: against the ideal split product (fp32 accumulation only, exact zeros included) for every r, against
+# fp64 while the format holds the row (bf16x6: always; fp16x3: r <= 20, tests/test_split_rows_host.py).
+def _split_operand(parts, t2d, rows, c):
+    """a (rows, c) fp32 device matrix -> (its parts [rows][parts c], its magnitude word or None)"""
+    dt = torch.bfloat16 if parts == 3 else torch.float16
+    am = _amax_word(t2d, rows, c) if parts == 2 else None
+    return ops.split_rows(parts, t2d, torch.empty(rows * parts * c, dtype=dt, device=DEV), rows, c, amax=am), am
+
+
+@pytest.mark.parametrize("parts", [3, 2])
+def test_conv3x3_wgrad_split_per_output_channel_over_mixed_magnitudes(parts):
+    """dy's channels at 2^-r of its maximum -> rows dW[cout] (n = 2, 9 x 11, 64 -> 256: the smallest shape of the split tests)"""
+    n, h, w, cin, cout = 2, 9, 11, 64, 256
+    dt = torch.bfloat16 if parts == 3 else torch.float16
+    x = torch.relu(rnd(n, h, w, cin, seed=510) * 2.0)
+    dy, r = rows_at_exponents(rnd(n, h, w, cout, seed=511), 3)
+    xd, dyd = x.to(DEV), dy.to(DEV)
+    ax = _amax_word(xd, n * h * w, cin) if parts == 2 else None
+    ady = _amax_word(dyd, n * h * w, cout) if parts == 2 else None
+    _, xps = ops.padded_bf16_alloc(n, h, w, parts * cin, DEV, dtype=dt)
+    ops.split_padded(parts, xd, None, None, xps, n, h, w, cin, amax=ax)
+    _, dyps = ops.padded_bf16_alloc(n, h, w, parts * cout, DEV, dtype=dt)
+    ops.split_padded(parts, dyd, None, None, dyps, n, h, w, cout, amax=ady)
+    dw = torch.full((cout * 9 * cin,), float("nan"), device=DEV)
+    ops.conv3x3_wgrad_split(parts, xps, dyps, dw, n, h, w, cin, cout, oscale=ops.split_scales(ady, ax) if parts == 2 else None)
+
+    def wgrad(dy_, x_):
+        return torch.nn.grad.conv2d_weight(nchw(x_), (cout, cin, 3, 3), nchw(dy_), padding=1).permute(0, 2, 3, 1)
+    check_rows("conv3x3_wgrad_split", dw.view(cout, 3, 3, cin), ideal_split_product(wgrad, dy, x, parts), wgrad(dy.double(), x.double()), r, parts)
+
+
+_SMALLEST_SPLIT_LINEAR = {}
+
+
+def _smallest_split_linear(parts):
+    """the smallest (m, k, j) goalnet_linear_split_ok serves, found by asking it: each dimension minimised with the others generous"""
+    if parts not in _SMALLEST_SPLIT_LINEAR:
+        big = {"m": 1024, "k": 1 << 18, "j": 1024}
+        assert ops.linear_split_ok(parts, big["m"], big["k"], big["j"])
+        best = {}
+        for d, step in (("m", 8), ("k", 64), ("j", 8)):
+            best[d] = next(v for v in range(step, big[d] + 1, step) if ops.linear_split_ok(parts, *(v if e == d else big[e] for e in "mkj")))
+        assert ops.linear_split_ok(parts, best["m"], best["k"], best["j"])
+        _SMALLEST_SPLIT_LINEAR[parts] = (best["m"], best["k"], best["j"])
+    return _SMALLEST_SPLIT_LINEAR[parts]
+
+
+@pytest.mark.parametrize("parts", [3, 2])
+@pytest.mark.parametrize("which", ["fwd", "dx", "dw"])
+def test_linear_split_per_row_over_mixed_magnitudes(which, parts):
+    """fwd: x's rows (frames) at 2^-r -> rows y[m], zero bias and no ReLU; dx: dy's rows (frames) -> rows dx[m]; dw: dy's columns
+    (output units) -> rows dW[j] — at the smallest (m, k, j) the split linear kernels serve"""
+    m, k, j = _smallest_split_linear(parts)
+    osc = (lambda a, b_: ops.split_scales(a, b_)) if parts == 2 else (lambda a, b_: None)
+    if which == "fwd":
+        x, r = rows_at_exponents(rnd(m, k, seed=520), 0)
+        w = rnd(j, k, seed=521) * 0.02
+        xs, ax = _split_operand(parts, x.to(DEV), m, k)
+        wsp, aw = _split_operand(parts, w.to(DEV), j, k)
+        y = torch.full((m, j), float("nan"), device=DEV)
+        ops.linear_fwd_split(parts, xs, wsp, torch.zeros(j, device=DEV), y, m, k, j, relu=False, oscale=osc(ax, aw))
+        check_rows("linear_fwd_split", y, ideal_split_product(lambda a, b_: a @ b_.t(), x, w, parts), x.double() @ w.double().t(), r, parts)
+    elif which == "dx":
+        dy, r = rows_at_exponents(rnd(m, j, seed=522), 0)
+        w = rnd(j, k, seed=521) * 0.02
+        dys, ady = _split_operand(parts, dy.to(DEV), m, j)
+        wsp, aw = _split_operand(parts, w.to(DEV), j, k)
+        dx = torch.full((m, k), float("nan"), device=DEV)
+        ops.linear_bwd_dx_split(parts, dys, wsp, dx, m, k, j, oscale=osc(ady, aw))
+        check_rows("linear_bwd_dx_split", dx, ideal_split_product(lambda a, b_: a @ b_, dy, w, parts), dy.double() @ w.double(), r, parts)
+    else:
+        dy, r = rows_at_exponents(rnd(m, j, seed=523), 1)
+        x = rnd(m, k, seed=520)
+        dys, ady = _split_operand(parts, dy.to(DEV), m, j)
+        xs, ax = _split_operand(parts, x.to(DEV), m, k)
+        dw = torch.full((j, k), float("nan"), device=DEV)
+        ops.linear_bwd_dw_split(parts, dys, xs, dw, m, k, j, oscale=osc(ady, ax))
+        check_rows("linear_bwd_dw_split", dw, ideal_split_product(lambda a, b_: a.t() @ b_, dy, x, parts), dy.double().t() @ x.double(), r, parts)

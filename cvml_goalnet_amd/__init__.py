@@ -13,6 +13,7 @@ from . import optim  # noqa: F401
 from .summarize import VideoSummarizer, VideoSummary  # noqa: F401
 from . import groundtruth  # noqa: F401
 from .segment import Segmentation, TemporalSegmenter  # noqa: F401
+from .rankcorr import HumanConsistency, RankCorrelation, RankEvaluator, rank_correlation  # noqa: F401
 
 __all__ = ["AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
-           "Segmentation"]
+           "Segmentation", "RankEvaluator", "RankCorrelation", "HumanConsistency", "rank_correlation"]

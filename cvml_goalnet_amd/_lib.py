@@ -143,6 +143,7 @@ PROTOTYPES = {
     "goalnet_gather_clips": (c_int, [P, c_int, c_int64, P, P, c_int, P, c_int64, P, P, P, P, c_size_t, P]),
     "goalnet_kts_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "goalnet_kts": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "goalnet_rank_corr": (c_int, [P, c_int64, c_int, P, c_int64, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
     "goalnet_knapsack_ws_bytes": (c_size_t, [c_int, c_int]),
     "goalnet_knapsack": (c_int, [P, P, c_int, c_int, P, P, c_size_t, P]),
     "goalnet_fscore": (c_int, [P, P, c_int, c_int, P, P, P]),

@@ -515,6 +515,27 @@ int goalnet_kts(const float* x, int n, int d, int normalize, int max_cp, int lmi
                 int full_n_frames, int32_t* change_points, int32_t* n_clips, int32_t* cps_samples, double* cost, double* objective,
                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- how good the importances are: Kendall's tau-b and Spearman's rho against every annotator, ties included ---------------
+ * EXTENSION, PARITY UNPINNED (no reference code): the reference reports the knapsack F-score only (utils.py:552-643). The oracle
+ * is scipy.stats.kendalltau (variant b) / spearmanr through fixtures, and the project's restatement (tests/rankcorr_ref.py,
+ * DESIGN.md 4.9) for the integer counts. For prediction row b and annotator a, over i = 0 .. n-1:
+ *     x_b[i] = x[b ldx + i / x_repeat]        y_a[i] = y[a ldy + i y_stride]
+ * (sampled frames: x_repeat = 1, y_stride = skip_frames, n = n_sampled; every frame: x_repeat = skip_frames, y_stride = 1,
+ * n = full_n_frames, which is expand_array of utils.py:396-410 applied to the predictions). Comparisons are IEEE < and == on the
+ * float32 values (-0.0 ties with 0.0). counts [batch][n_annotators][8] int64, an OUTPUT that doubles as the accumulator (the call
+ * zeroes it on `stream` first): S = concordant - discordant unordered pairs, tx / ty / txy = pairs tied in x / in y / in both,
+ * cxy = sum dx dy, cxx = sum dx^2, cyy = sum dy^2 with d = 2 #less + #equal (self included) - n (twice the average rank minus
+ * n + 1), bad = the number of i with a non-finite x or y. All of it exact integer arithmetic, independent of grid and order.
+ * With n0 = n (n - 1) / 2, in float64: tau [batch][n_annotators] = S / sqrt(double(n0 - tx) double(n0 - ty)), NaN where n < 2,
+ * n0 == tx, n0 == ty or bad > 0; rho = cxy / sqrt(double(cxx) double(cyy)), NaN where cxx == 0, cyy == 0 or bad > 0 (a constant
+ * input, where SciPy returns NaN). mean [batch][2] = the means of the defined tau and of the defined rho over the annotators,
+ * summed in annotator order (NaN when none is defined); n_valid [batch][2] int32 = how many were; status [batch] int32 = 1 when
+ * bad > 0 for any annotator of the row — a data condition, not a return code. 1 <= n <= 65536, 1 <= n_annotators <= 128,
+ * 1 <= batch <= 65535, x_repeat, y_stride >= 1, ldx >= ceil(n / x_repeat), ldy >= (n - 1) y_stride + 1; no pointer is nullable;
+ * counts, tau, rho and mean 8-byte aligned. One memset and two launches on `stream`, no allocation, no synchronisation. */
+int goalnet_rank_corr(const float* x, int64_t ldx, int x_repeat, const float* y, int64_t ldy, int y_stride, int batch, int n_annotators,
+                      int n, int64_t* counts, double* tau, double* rho, double* mean, int32_t* n_valid, int32_t* status, void* stream);
+
 /* up to GOALNET_ROWCOPY_MAX gathers (gather != 0: dst[0:nrows] = src[c : c + nrows]) and scatters
  * (gather == 0: dst[c : c + nrows] = src[0:nrows]) in one launch; c = *cursor + cursor_bias */
 #define GOALNET_ROWCOPY_MAX 4

@@ -44,6 +44,7 @@ class VideoTrainer:
         self.graphs = graphs
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
+        self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
         self._pool = None
         self._cap = 0                               # frames the staging tables hold
@@ -61,6 +62,7 @@ class VideoTrainer:
         cap = max(n_frames, 2 * self._cap if key == self._key else 0, 64)
         self._graphs.clear()                        # pointers below are baked into captured graphs
         self._uses_w5b.clear()
+        self._shadows.clear()
         self._pool = None
         self._key, self._cap = key, cap
         sb = self.subbatch_size
@@ -124,6 +126,13 @@ class VideoTrainer:
             self._sub_step(n)
             self.eager_steps += 1
             return
+        if g is not None and not self._shadows.get(gkey) and m._w5b is not None and m._w5b_version == m._w5_version():
+            # While the 16-bit copy is live the fused Adam of EVERY step refreshes it beside the fp32 master, also of a <= 16-row step
+            # that never reads it. This graph was captured before the copy existed (or while it was stale): its Adam launch has no
+            # shadow, so a replay would leave the copy one step behind under a valid version stamp and the next > 16-row step
+            # would read it. Capture the size again, now with the shadow.
+            del self._graphs[gkey]
+            g = None
         if g is None:
             if gkey not in self._seen:              # first step of this size: eager (allocates Adam state, operand buffers)
                 self._seen.add(gkey)
@@ -144,7 +153,8 @@ class VideoTrainer:
             for i, v in zip((1, 2, 3), nbt):
                 getattr(m.visbl, f"bnorm{i}").num_batches_tracked.fill_(v)
             self._graphs[gkey] = g
-            self._uses_w5b[gkey] = m._w5b is not None and m._w5b_version == m._w5_version() and m.last_used_w5b
+            self._shadows[gkey] = m._w5b is not None and m._w5b_version == m._w5_version()
+            self._uses_w5b[gkey] = self._shadows[gkey] and m.last_used_w5b
         g.replay()
         self._host_bookkeeping_after_replay()
         self.replays += 1

@@ -76,16 +76,16 @@ def decisions(inter, taps, gates, drop_masks, mlp=True):
     return out
 
 
-def storage_noise(p, b, audio, visual, drop_masks, inter, dtype):
+def storage_noise(p, b, audio, visual, drop_masks, inter, dtype, head="regression", training=True):
     """b_layer of every layer with a decision: twice the largest change of its pre-activation when the oracle's forward is run once more
     with every tensor that a 16-bit mode stores in 16 bits (the conv outputs y — hence the pooled p — of blocks 2 and 3,
     the BatchNorm-applied GEMM operands of conv2, conv3 and linear5, and those GEMMs' weight operands) rounded through `dtype` where it
-    is stored. `inter`: the plain forward on the same inputs. The factor 2: the device's fp32 accumulation order and its own routing
+    is stored. `inter`: the plain forward on the same inputs (same `head`, same `training`). The factor 2: the device's fp32 accumulation order and its own routing
     flips come on top of the storage rounding that this emulation models."""
     rounded = {}
     with torch.no_grad():
         avm_ref.forward(p, {k: v.clone() for k, v in b.items()}, audio, visual, drop_masks, audio is not None, rounded,
-                        store=lambda name, x: x.to(dtype).to(x.dtype) if name in STORED_16 else x)
+                        head=head, store=lambda name, x: x.to(dtype).to(x.dtype) if name in STORED_16 else x, training=training)
     keys = [f"visbl.conv{i}" for i in (1, 2, 3)] + list(MLP_LAYERS)
     return {k: 2.0 * float((rounded[k] - inter[k]).abs().max()) for k in keys}
 

@@ -1,0 +1,342 @@
+"""One fused step of ANY mode against the CPU oracle: what tests/test_gpu_bench_shapes.py::_run_case does with copies = 1, generalised to
+`head`, `audio_included` and train / eval mode, at 40 x 40 frames, bins = 30 and n in {10, 32} (n = 10: the skinny linear5, the fused MLP
+of the regression head, the one-launch BatchNorm kernels; n = 32: the 16-bit linear5 / p3 / y3 and the unfused MLP).
+
+Three parts, so that the comparison can be run — and broken on purpose — without a GPU (tests/test_mode_matrix_host.py):
+
+  fixture(...)        parameters, inputs, dropout masks and BatchNorm buffers of a cell: plain CPU tensors, cached, never modified
+  run_device(...)     the step on the device -> a dict of CPU tensors (what the device decided and computed), plus the assertions that
+                      only the device can answer (which kernels ran, which buffers moved)
+  compare(...)        that dict against the oracle under the adopted decisions; oracle_as_device(...) builds the same dict from an
+                      oracle run, which is how the host tests exercise compare()
+
+Tolerances: none is new. fp32: logits <= 2e-5 where no window is rerouted, predictions / loss <= 2e-5, every gradient within
+F32_FACTOR["fp32"] x the oracle's own fp32 distance from an fp64 run under the same decisions or within 2e-6 of the tensor's scale,
+updated parameters inside the Adam sensitivity bound. bf16 / fp16: TOL16[precision] for the logits, the weight gradients' relative L2
+under the adopted decisions, and predictions / loss / running statistics. Every adopted tap, conv gate and MLP gate goes through
+decisions() and judge() (fp32: NEAR_TIE; 16-bit: storage_noise measured from the reference).
+
+Eval cells run on the CONVERGED batch statistics of their own inputs, perturbed (mean by up to +-0.2 sigma, variance by up to e^+-0.3,
+seeded): with eval_ref.running_stats() (running_mean uniform in +-1.5 against pooled activations of order 0.1) the BatchNorm output is
+dominated by a constant, the output hardly depends on the frame, and a row mix-up stays under the 16-bit bounds (measured on the oracle
+alone: 5.8e-5 on the logits, 6e-3 .. 3e-2 on the gradients). The running buffers of a train-mode forward on fixed inputs
+and parameters move by r <- 0.9 r + 0.1 s with the same batch statistic s on every pass, so the value they converge to is s itself (the
+unbiased variance): it is taken from one fp64 oracle forward instead of iterating the update."""
+import functools
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+import eval_ref
+from _decisions import MLP_LAYERS, NEAR_TIE, decisions, judge, report_lines, storage_noise, totals
+from cvml_goalnet_amd import synth
+from oracle import avm_ref
+from test_gpu_avm import _is_reduction_grad
+from test_gpu_bench_shapes import F32_FACTOR, TOL16, _gates_first, _mlp_gates_first, _taps_first
+
+DEV = "cuda:0"
+H = 40
+LR = 1e-3
+CLASS_GAP = 4e-5          # fp32 cells: classes are compared on rows whose oracle top-2 score gap exceeds 2 x the 2e-5 score tolerance
+GUARD_GRADS = ("visbl.conv3.weight", "visbl.linear5.weight")
+# labels 2, 5, 3, 1, ... : the default seed gives frames 0 and 1 the SAME label (1, 1), and without audio and dropout nothing but its label
+# tells a row of the classifier's loss from another: swapping the two frames would be a symmetry of the step, invisible in every gradient
+LABEL_SEED = synth.BASE_SEED + 1
+
+Cell = namedtuple("Cell", "precision head audio mode n")
+
+# precision x head x audio x mode x n: every combination of levels of any three factors appears (asserted by
+# tests/test_mode_matrix_host.py). Written out by hand; nothing is generated at run time.
+CELLS = (
+    Cell("bf16", "classifier", False, "eval", 32),
+    Cell("bf16", "classifier", False, "train", 10),
+    Cell("bf16", "classifier", True, "eval", 10),
+    Cell("bf16", "regression", False, "train", 32),
+    Cell("bf16", "regression", True, "eval", 32),
+    Cell("bf16", "regression", True, "train", 10),
+    Cell("fp16", "classifier", False, "eval", 32),
+    Cell("fp16", "classifier", True, "eval", 10),
+    Cell("fp16", "classifier", True, "train", 32),
+    Cell("fp16", "regression", False, "train", 10),
+    Cell("fp16", "regression", True, "eval", 32),
+    Cell("fp32", "classifier", False, "train", 10),
+    Cell("fp32", "classifier", True, "eval", 32),
+    Cell("fp32", "regression", False, "eval", 10),
+    Cell("fp32", "regression", False, "train", 32),
+    Cell("fp32", "regression", True, "train", 10),
+)
+
+
+def cell_id(c):
+    return f"{c.precision}-{c.head}-{'audio' if c.audio else 'noaudio'}-{c.mode}-n{c.n}"
+
+
+def is_fp32(c):
+    return c.precision == "fp32"
+
+
+def h16_of(c):
+    return torch.bfloat16 if c.precision == "bf16" else torch.float16
+
+
+# ---- fixtures --------------------------------------------------------------------------------------------------------------------
+def converged_stats(p, aud, vis, audio, head, seed=2025):
+    """BatchNorm buffers of an eval cell: the batch statistics of the cell's own inputs — what the running buffers of the reference's
+    train-mode forward (no dropout) converge to, see the module docstring — perturbed by a seeded factor: the mean by up to +-0.2 sigma,
+    the variance by up to e^+-0.3. num_batches_tracked = 7, as in the eval fixtures."""
+    inter = {}
+    with torch.no_grad():
+        avm_ref.forward({k: v.double() for k, v in p.items()}, avm_ref.init_buffers(torch.float64), None if aud is None else aud.double(),
+                        vis.double(), None, audio, inter, head=head)
+    rng = np.random.RandomState(seed)
+    b = {}
+    for i in (1, 2, 3):
+        x = inter[f"visbl.maxpool{i}"]
+        mean, var = x.mean((0, 2, 3)), x.var((0, 2, 3), unbiased=True)
+        c = mean.numel()
+        mean = mean + torch.from_numpy(rng.uniform(-0.2, 0.2, c)) * var.sqrt()
+        var = var * torch.from_numpy(np.exp(rng.uniform(-0.3, 0.3, c)))
+        b[f"visbl.bnorm{i}.running_mean"] = mean.float()
+        b[f"visbl.bnorm{i}.running_var"] = var.float()
+        b[f"visbl.bnorm{i}.num_batches_tracked"] = torch.tensor(7, dtype=torch.int64)
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def fixture(head, audio, mode, n):
+    """everything a cell starts from, as CPU tensors that nobody modifies (callers clone what a step updates in place)"""
+    params = eval_ref.classifier_params(H, audio) if head == "classifier" else synth.make_params(H, H, 30, audio)
+    fx = {"p": {k: torch.from_numpy(v.copy()) for k, v in params.items()},
+          "vis": torch.from_numpy(synth.make_visual(n, H, H)),
+          "aud": torch.from_numpy(synth.make_audio(n)) if audio else None,
+          "lab": torch.from_numpy(synth.make_labels(n, seed=LABEL_SEED))}
+    if mode == "train":
+        fx["masks"] = [torch.from_numpy(m) for m in synth.make_drop_masks(n, step=0)]
+        fx["b"] = avm_ref.init_buffers()
+    else:
+        fx["masks"] = None
+        fx["b"] = converged_stats(fx["p"], fx["aud"], fx["vis"], audio, head)
+    return fx
+
+
+def fixture_of(c):
+    return fixture(c.head, c.audio, c.mode, c.n)
+
+
+def loss_fn(c):
+    return avm_ref.ce_loss if c.head == "classifier" else avm_ref.mse_bcast
+
+
+def _clone(d):
+    return {k: v.clone() for k, v in d.items()}
+
+
+# ---- the oracle as a stand-in for the device (host tests) ------------------------------------------------------------------------
+def oracle_as_device(c, fx, vis=None, training=None):
+    """the dict run_device() returns, computed by the fp32 oracle with its OWN decisions. `vis` / `training` override the cell's visual
+    input / mode: that is how tests/test_mode_matrix_host.py hands compare() a wrong "device"."""
+    vis = fx["vis"] if vis is None else vis
+    training = (c.mode == "train") if training is None else training
+    p, b = _clone(fx["p"]), _clone(fx["b"])
+    inter = {}
+    loss, pred, g = avm_ref.train_step(p, b, {}, fx["aud"], vis, fx["lab"], fx["masks"], c.audio, inter, head=c.head, training=training)
+    taps, gates = {}, {}
+    for i in (1, 2, 3):
+        taps[i] = avm_ref.natural_taps(inter[f"visbl.relu{i}"].detach())[0]
+        gates[i] = avm_ref._ForcedMaxPool.apply(inter[f"visbl.conv{i}"].detach(), taps[i]) > 0
+    for key in MLP_LAYERS:
+        gates[key] = inter[key].detach() > 0
+    scores = pred if c.head == "classifier" else pred.view(-1)
+    return {"loss": float(loss), "pred": scores, "logit": inter["logit"].detach().reshape(c.n, -1), "taps": taps, "gates": gates,
+            "grads": g, "params": p, "bufs": b,
+            "classes": (torch.argmax(pred, dim=1) + 1).float() if c.head == "classifier" else None}
+
+
+# ---- the gradient criterion, one function for compare() and for the sensitivity guard --------------------------------------------------
+def grad_verdict(c, name, mine, og, g64=None):
+    """the cell's criterion for one gradient tensor `mine` against the oracle's `og` (fp32 cells: and the fp64 truth `g64` under the same
+    decisions). Returns (figure for the log, failure message or None). 16-bit cells hold the weight gradients to TOL16's relative L2;
+    bias / BatchNorm-affine gradients (cancelling sums: test_gpu_avm._is_reduction_grad) carry no bound there, as in _run_case."""
+    scale = max(og.abs().max().item(), 1e-30)
+    if is_fp32(c):
+        e_ref = (og.double() - g64).abs().max().item()
+        e_dev = (mine.double() - g64).abs().max().item()
+        bad = e_dev > max(F32_FACTOR["fp32"] * e_ref, 2e-6 * scale)
+        return e_dev / scale, (f"{name}: gradient is {e_dev:.3e} from the fp64 truth, the oracle's fp32 path {e_ref:.3e} (max|g| {scale:.3e})"
+                               if bad else None)
+    if _is_reduction_grad(name):
+        return (mine - og).abs().max().item() / scale, None
+    l2 = ((mine.double() - og.double()).norm() / og.double().norm().clamp_min(1e-30)).item()
+    bad = l2 > TOL16[c.precision][1]
+    return l2, f"{name}: {c.precision}-mode gradient relative L2 error {l2:.3e} > {TOL16[c.precision][1]}" if bad else None
+
+
+def oracle_grads(c, fx, vis=None, dtype=torch.float32, taps=None, gates=None):
+    """gradients (and prediction) of the oracle's step in `dtype`, parameters left alone"""
+    vis = fx["vis"] if vis is None else vis
+    p = {k: v.to(dtype, copy=True).requires_grad_(True) for k, v in fx["p"].items()}
+    b = {k: (v.to(dtype) if v.is_floating_point() else v.clone()) for k, v in fx["b"].items()}
+    masks = None if fx["masks"] is None else [m.to(dtype) for m in fx["masks"]]
+    pred = avm_ref.forward(p, b, None if fx["aud"] is None else fx["aud"].to(dtype), vis.to(dtype), masks, c.audio, None,
+                           pool_taps=taps, head=c.head, relu_gates=gates, training=c.mode == "train")
+    loss_fn(c)(pred, fx["lab"].to(dtype)).backward()
+    return {k: v.grad for k, v in p.items()}, pred.detach()
+
+
+# ---- the comparison ----------------------------------------------------------------------------------------------------------------
+def compare(c, fx, dev, log=print):
+    """`dev` (run_device / oracle_as_device) against the oracle under the decisions `dev` carries. Collects every failure and asserts at
+    the end; returns the figures of the DESIGN.md §5 table."""
+    fp32, train = is_fp32(c), c.mode == "train"
+    tag = f"[matrix] {cell_id(c)}"
+    p, b = _clone(fx["p"]), _clone(fx["b"])
+    aud, vis, lab, masks = fx["aud"], fx["vis"], fx["lab"], fx["masks"]
+    taps = dev["taps"]
+    # fp32 adopts the conv blocks' gates; the 16-bit modes also linear5's and the fusion layers' (see _run_case)
+    gates = {k: v for k, v in dev["gates"].items() if not fp32 or k in (1, 2, 3)}
+    failures = []
+
+    # the oracle's own forward: logits, and the judge of every adopted decision
+    inter = {}
+    with torch.no_grad():
+        avm_ref.forward(p, _clone(b), aud, vis, masks, c.audio, inter, head=c.head, training=train)
+    ref_logit = inter["logit"].reshape(c.n, -1)
+    found = decisions(inter, taps, gates, masks, mlp=not fp32)
+    (nd, worst), (ng, gworst) = totals(found, "tap"), totals(found, "gate")
+    noise = None if fp32 else storage_noise(p, b, aud, vis, masks, inter, h16_of(c), head=c.head, training=train)
+    del inter
+    for line in report_lines(found, noise):
+        log(f"{tag} decisions, {line}")
+    failures += judge(found, noise)
+    n_dis = sum(v[0] for v in found.values())
+    w_dis = max([v[1] / max(v[2], 1e-30) for v in found.values() if v[0]], default=0.0)
+    e_logit = (dev["logit"] - ref_logit).abs().max().item()
+    if fp32:
+        if worst > NEAR_TIE:
+            failures.append("max-pool argmax differs from ATen's where the window is NOT a near-tie")
+        if gworst > NEAR_TIE:
+            failures.append("the ReLU gate at a window's argmax differs from the oracle's where y is NOT within rounding of zero")
+        if nd == 0 and e_logit > 2e-5:
+            failures.append(f"logits {e_logit:.3e} from the oracle's with no window rerouted")
+    elif e_logit > TOL16[c.precision][0]:
+        failures.append(f"{c.precision} logits outside the tolerance: {e_logit:.3e} > {TOL16[c.precision][0]}")
+
+    g64 = pred64 = None
+    if fp32:
+        g64, pred64 = oracle_grads(c, fx, dtype=torch.float64, taps=taps, gates=gates)
+    o_loss, o_pred, o_g = avm_ref.train_step(p, b, {}, aud, vis, lab, masks, c.audio, pool_taps=taps, head=c.head, relu_gates=gates,
+                                             training=train)
+    o_pred = o_pred.reshape(c.n, -1)
+    d_pred = dev["pred"].reshape(c.n, -1)
+    tol = 2e-5 if fp32 else TOL16[c.precision][2]
+    perr = (d_pred - o_pred).abs().max().item()
+    lerr = abs(dev["loss"] - o_loss.item()) / max(1.0, abs(o_loss.item()))
+    log(f"{tag}: logit error {e_logit:.2e}; |pred - oracle| {perr:.2e}, loss rel err {lerr:.2e} (same decisions); "
+        f"{nd} windows rerouted (worst gap {worst:.2e} of max|y|), {ng} conv gates differ (worst |y| {gworst:.2e})")
+    if perr > tol:
+        failures.append(f"predictions / scores {perr:.3e} from the oracle's > {tol}")
+    if lerr > tol:
+        failures.append(f"loss relative error {lerr:.3e} > {tol}")
+    if fp32:
+        e_ref = (o_pred.double() - pred64.reshape(c.n, -1)).abs().max().item()
+        e_dev = (d_pred.double() - pred64.reshape(c.n, -1)).abs().max().item()
+        if e_dev > max(F32_FACTOR["fp32"] * e_ref, 2e-6):
+            failures.append(f"predictions are {e_dev:.3e} from the fp64 truth, the oracle's fp32 path {e_ref:.3e}")
+    if c.head == "classifier":
+        if not torch.equal(dev["classes"], (torch.argmax(d_pred, dim=1) + 1).float()):
+            failures.append("predict_classes(scores) is not argmax + 1 of the device's own scores")
+        if fp32:
+            top2 = o_pred.topk(2, dim=1).values
+            gap = (top2[:, 0] - top2[:, 1])
+            assert gap.min().item() > CLASS_GAP, (f"the oracle alone leaves a row with a top-2 score gap of {gap.min().item():.2e} "
+                                                  f"<= {CLASS_GAP}: change the seed (no row may be excluded)")
+            if not torch.equal(dev["classes"], (torch.argmax(o_pred, dim=1) + 1).float()):
+                failures.append(f"classes differ from the oracle's (smallest oracle top-2 gap {gap.min().item():.2e})")
+
+    report = []
+    for name, og in o_g.items():
+        mine = dev["grads"][name].reshape(og.shape)
+        fig, bad = grad_verdict(c, name, mine, og, None if g64 is None else g64[name])
+        report.append((fig, name, not fp32 and not _is_reduction_grad(name)))
+        if bad:
+            failures.append(bad)
+        if fp32:
+            # Adam sensitivity: lr * |dg| / (|g| + eps), at most 2 lr (tests/test_gpu_avm.py)
+            bound = (mine - og).abs().mul_(8.0).div_(og.abs().add_(1e-8)).clamp_(max=2.0).mul_(LR).add_(2e-6)
+            over = ((dev["params"][name].reshape(og.shape) - p[name]).abs() - bound).max().item()
+            if over > 0:
+                failures.append(f"{name}: after Adam exceeds its sensitivity bound vs oracle by {over:.3e}")
+    report.sort(reverse=True)
+    for fig, name, l2 in report[:6] if fp32 else report:
+        log(f"{tag}     {fig:.3e}  {name}{' [relative L2]' if l2 else ''}")
+    bounded = [r for r in report if fp32 or r[2]]
+
+    # BatchNorm buffers. train: the oracle's updated ones; eval: bit-unchanged
+    for k, v0 in fx["b"].items():
+        got = dev["bufs"][k]
+        if not train:
+            if not torch.equal(got, v0):
+                failures.append(f"{k} changed under eval()")
+        elif k.endswith("num_batches_tracked"):
+            if int(got) != int(v0) + 1:
+                failures.append(f"{k} is {int(got)} after one train step from {int(v0)}")
+        else:
+            t = 1e-5 if fp32 else TOL16[c.precision][2]
+            atol = t * b[k].abs().max().item() if k.endswith("running_mean") else 1e-7
+            if not torch.allclose(got.double(), b[k].double(), rtol=t, atol=atol):
+                failures.append(f"{k} differs from the oracle's by {(got - b[k]).abs().max().item():.3e}")
+    assert not failures, f"{cell_id(c)}:\n" + "\n".join(failures)
+    return {"logit": e_logit, "grad": bounded[0][0], "grad_name": bounded[0][1], "disagree": n_dis, "worst": w_dis}
+
+
+# ---- the device ----------------------------------------------------------------------------------------------------------------------
+def run_device(c, fx, monkeypatch):
+    """one train_step of the cell on the GPU. Returns the dict compare() reads; asserts what only the device can answer: the kernels the
+    mode selects ran (non-vacuity), eval mode moved no counter, fp16 overflowed nowhere."""
+    from cvml_goalnet_amd import AVM
+    from test_gpu_eval import Counter
+    train, half = c.mode == "train", not is_fp32(c)
+    m = AVM(audio_included=c.audio, device=DEV, seed=synth.BASE_SEED, head=c.head, precision=c.precision)
+    sd = _clone(fx["p"])
+    sd.update(_clone(fx["b"]))
+    m.load_state_dict(sd)
+    if train:
+        m.set_dropout_masks(fx["masks"])
+    else:
+        m.dropout_mode = "device"              # live dropout: eval() itself must switch it off
+        m.eval()
+    m.keep_ctx = True
+    pool_eval, pool_stats = Counter(monkeypatch, "pool_bn_eval_fwd"), Counter(monkeypatch, "pool_bnstats_fwd")
+    drop0 = m._drop_step
+    ctr0 = None if m._state is None else m._state.tolist()
+    loss, pred = m.train_step(None if fx["aud"] is None else fx["aud"].to(DEV), fx["vis"].to(DEV), fx["lab"].to(DEV), lr=LR)
+    torch.cuda.synchronize()
+    ctx = m.last_ctx
+    m.last_ctx = None
+    n = c.n
+    # non-vacuity: the kernels this cell is in the matrix for
+    big16 = half and n > 16
+    assert m.last_used_w5b == big16, "linear5 ran on the other engine than the cell expects"
+    assert ("xh3" in ctx) == big16, "xh3 is in the context exactly when linear5 ran on 16-bit operands"
+    assert m._mlp_fused(n) == (n <= 16 and c.head == "regression")
+    assert ctx["eval"] == (not train)
+    if c.precision == "fp16":
+        assert m._guard.tolist() == [0, 0], "the automatic loss scale overflowed"
+    if not train:
+        assert pool_eval.calls == 3 and pool_stats.calls == 0, (pool_eval.calls, pool_stats.calls)
+        assert m._drop_step == drop0, "the dropout counter moved under eval()"
+        assert int(m._state[1]) == (0 if ctr0 is None else ctr0[1]), "the device's dropout counter moved under eval()"
+    else:
+        assert pool_eval.calls == 0
+    assert pred.shape == ((n, eval_ref.CLS_C) if c.head == "classifier" else (n,))
+    assert m.last_logit.shape == ((n, eval_ref.CLS_C) if c.head == "classifier" else (n,)), "last_logit is (n, C) under the classifier head"
+    gates = _gates_first(ctx, n)
+    gates.update(_mlp_gates_first(ctx, n, ctx["hs"][0].shape[1] - 512))
+    sd1 = m.state_dict()
+    dev = {"loss": loss.item(), "pred": pred.cpu(), "logit": m.last_logit.cpu().reshape(n, -1), "taps": _taps_first(ctx, n), "gates": gates,
+           "grads": {k: m.grad_of(k).cpu() for k in fx["p"]}, "params": {k: sd1[k].cpu() for k in fx["p"]},
+           "bufs": {k: sd1[k].cpu() for k in fx["b"]},
+           "classes": m.predict_classes(pred).cpu() if c.head == "classifier" else None}
+    del ctx
+    return dev

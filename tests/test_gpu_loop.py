@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import eval_ref  # noqa: E402
 from _golden import Golden  # noqa: E402
 from cvml_goalnet_amd import AVM, ops, synth  # noqa: E402
 from cvml_goalnet_amd.loop import VideoTrainer  # noqa: E402
@@ -21,9 +22,9 @@ DEV = "cuda:0"
 LR = 1e-3
 
 
-def load_model(h, audio, precision="fp32"):
-    params = synth.make_params(h, h, 30, audio)
-    m = AVM(audio_included=audio, device=DEV, precision=precision, seed=synth.BASE_SEED)
+def load_model(h, audio, precision="fp32", head="regression"):
+    params = eval_ref.classifier_params(h, audio) if head == "classifier" else synth.make_params(h, h, 30, audio)
+    m = AVM(audio_included=audio, device=DEV, precision=precision, seed=synth.BASE_SEED, head=head)
     sd = {k: torch.from_numpy(v) for k, v in params.items()}
     sd.update(avm_ref.init_buffers())
     m.load_state_dict(sd)
@@ -98,30 +99,88 @@ def _video(n, h, audio, salt):
     return aud, vis, lab
 
 
-@pytest.mark.parametrize("audio,precision", [(True, "fp32"), (False, "fp32"), (True, "bf16")])
-def test_graph_loop_equals_eager_train_steps_bit_for_bit(audio, precision):
+def _loop_counts(frames, sb):
+    """(eager steps, graph replays) of VideoTrainer on videos of `frames` frames with nobody writing the model in between: a sub-batch
+    size runs eagerly the first time it occurs (allocations), is captured the second time, and is a replay from then on"""
+    seen, eager, replays = set(), 0, 0
+    for f in frames:
+        for off in range(0, f, sb):
+            n = min(sb, f - off)
+            eager, replays = (eager, replays + 1) if n in seen else (eager + 1, replays)
+            seen.add(n)
+    return eager, replays
+
+
+@pytest.mark.parametrize("audio,precision,head,sb", [
+    pytest.param(True, "fp32", "regression", 10, id="True-fp32"), pytest.param(False, "fp32", "regression", 10, id="False-fp32"),
+    pytest.param(True, "bf16", "regression", 10, id="True-bf16"), pytest.param(False, "bf16", "regression", 10, id="False-bf16"),
+    pytest.param(True, "fp16", "regression", 10, id="True-fp16"), pytest.param(False, "fp16", "regression", 10, id="False-fp16"),
+    pytest.param(True, "fp32", "classifier", 10, id="True-fp32-classifier"),
+    pytest.param(False, "bf16", "classifier", 10, id="False-bf16-classifier"),
+    # sub-batches of 20 (> 16 rows): the captured graph holds the 16-bit linear5 / p3 / y3 kernels and the shadowed Adam
+    pytest.param(True, "bf16", "regression", 20, id="True-bf16-sb20"), pytest.param(True, "fp16", "regression", 20, id="True-fp16-sb20")])
+def test_graph_loop_equals_eager_train_steps_bit_for_bit(audio, precision, head, sb):
     h = 40
-    videos = [_video(47, h, audio, 1), _video(33, h, audio, 2)]       # 4x10 + 7, then 3x10 + 3
-    eager, graphed = load_model(h, audio, precision), load_model(h, audio, precision)
-    tr = VideoTrainer(graphed, subbatch_size=10, lr=LR)
+    frames = (47, 33)                                                # sb = 10: 4x10 + 7, then 3x10 + 3; sb = 20: 2x20 + 7, then 20 + 13
+    videos = [_video(frames[0], h, audio, 1), _video(frames[1], h, audio, 2)]
+    eager, graphed = load_model(h, audio, precision, head), load_model(h, audio, precision, head)
+    tr = VideoTrainer(graphed, subbatch_size=sb, lr=LR)
     for aud, vis, lab in videos:
         # eager: the reference's loop, main.py:177-196, on GPU tensors
         e_loss, e_pred = [], []
-        for a in range(0, vis.shape[0], 10):
-            b = min(a + 10, vis.shape[0])
+        for a in range(0, vis.shape[0], sb):
+            b = min(a + sb, vis.shape[0])
             loss, pred = eager.train_step(aud[a:b].to(DEV) if audio else None, vis[a:b].to(DEV), lab[a:b].to(DEV), lr=LR)
             e_loss.append(loss)
-            e_pred.append(pred)
+            e_pred.append(eager.predict_classes(pred) if head == "classifier" else pred)     # main.py:190: argmax + 1 is collected
         losses, preds = tr.train_video(aud, vis, lab)
         torch.cuda.synchronize()
         assert torch.equal(losses, torch.cat(e_loss))
         assert torch.equal(preds, torch.cat(e_pred))
-    assert tr.replays >= 6 and tr.eager_steps == 3, (tr.replays, tr.eager_steps)   # sizes 10, 7, 3 ran eagerly once each
+    want_eager, want_replays = _loop_counts(frames, sb)               # sb = 10: sizes 10, 7, 3 ran eagerly once each, 6 replays
+    steps = want_eager + want_replays
+    assert (want_eager, want_replays) == {10: (3, 6), 20: (3, 2)}[sb]
+    assert tr.replays == want_replays and tr.eager_steps == want_eager, (tr.replays, tr.eager_steps)
+    assert sorted(k[0] for k in tr._graphs) == [sb], "the full-size sub-batch is the one captured graph"
+    assert any(tr._uses_w5b.values()) == (sb > 16 and precision != "fp32"), "a graph of > 16 rows of a 16-bit mode reads the 16-bit weights"
     sd_e, sd_g = eager.state_dict(), graphed.state_dict()
     for k in sd_e:
         assert torch.equal(sd_e[k], sd_g[k]), k
-    assert graphed._state.tolist()[:2] == [9, 9] and graphed._adam_t == 9 and graphed._drop_step == 9
+    assert graphed._state.tolist()[:2] == [steps, steps] and graphed._adam_t == steps and graphed._drop_step == steps
     assert torch.equal(graphed._adam_m, eager._adam_m) and torch.equal(graphed._adam_v, eager._adam_v)
+    if precision == "fp16":
+        assert graphed._guard.tolist() == [0, 0] and eager._guard.tolist() == [0, 0]
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+def test_16bit_graph_of_a_small_sub_batch_keeps_the_16bit_weight_copy_fresh(precision):
+    """Two 7-frame videos first: the 7-row step (fp32 weight-streaming linear5) is captured BEFORE the 16-bit copy of linear5.weight
+    exists, so that graph's fused Adam updates the fp32 master only. Then 47 frames in sub-batches of 20: the 20-row steps create the
+    copy and keep it fresh through their own shadowed Adam, the 7-row tail follows them, and the next 20-row step reads the copy. The
+    graph captured without the shadow must not be replayed once the copy is live (its Adam would leave the copy one step behind
+    with a valid version stamp: before VideoTrainer captured such a size again, the last video's loss differed from the eager one
+    in the fourth digit); compared bit for bit with eager train_step calls, whose Adam looks at the copy on every step."""
+    h, sb, frames = 40, 20, (7, 7, 47, 20)
+    eager, graphed = load_model(h, True, precision), load_model(h, True, precision)
+    tr = VideoTrainer(graphed, subbatch_size=sb, lr=LR)
+    for vi, f in enumerate(frames):
+        aud, vis, lab = _video(f, h, True, 30 + vi)
+        e_loss, e_pred = [], []
+        for a in range(0, f, sb):
+            b = min(a + sb, f)
+            loss, pred = eager.train_step(aud[a:b].to(DEV), vis[a:b].to(DEV), lab[a:b].to(DEV), lr=LR)
+            e_loss.append(loss); e_pred.append(pred)
+        losses, preds = tr.train_video(aud, vis, lab)
+        torch.cuda.synchronize()
+        assert torch.equal(losses, torch.cat(e_loss)), f"video {vi}"
+        assert torch.equal(preds, torch.cat(e_pred)), f"video {vi}"
+    sd_e, sd_g = eager.state_dict(), graphed.state_dict()
+    for k in sd_e:
+        assert torch.equal(sd_e[k], sd_g[k]), k
+    assert torch.equal(graphed._w5b, eager._w5b), "the 16-bit copy of linear5.weight"
+    # 7 (eager), 7 (captured without the shadow), 20 (eager), 20 (captured), 7 (the copy is live: captured again, with it), 20 (replay)
+    assert tr.eager_steps == 2 and tr.replays == 4, (tr.eager_steps, tr.replays)
+    assert all(tr._shadows.values()) and len(tr._graphs) == 2
 
 
 def test_bf16_graph_loop_survives_writers_outside_the_graph():

@@ -1,0 +1,189 @@
+"""CPU: what the mode matrix (tests/test_gpu_mode_matrix.py, tests/_mode_case.py) rests on, checked without a GPU.
+
+  * the oracle's eval path (oracle/avm_ref.py: training=False) is the eval restatement (tests/eval_ref.py), bit for bit, reproduces the
+    eval fixtures captured from the reference within the bounds of tests/test_eval_golden.py, leaves the buffers alone and ignores
+    dropout masks;
+  * the committed list of cells covers every combination of levels of any three of its five factors;
+  * SENSITIVITY GUARD: on every cell's inputs the cell's own gradient criterion rejects an oracle run with frames 0 and 1 of the visual
+    input swapped — a condition on the inputs and statistics (a cell whose output hardly depends on the frame could not see a row mix-up
+    on the device either), never a measurement of the device;
+  * DRY RUN of the runner's comparison: compare() accepts the oracle standing in for the device, and turns red when that stand-in ran
+    on swapped frames, or in train mode for an eval cell."""
+import itertools
+
+import pytest
+import torch
+
+import eval_ref
+from _golden import Golden
+from _mode_case import (CELLS, CLASS_GAP, GUARD_GRADS, TOL16, Cell, cell_id, compare, fixture_of, grad_verdict, is_fp32, oracle_as_device,
+                        oracle_grads)
+from cvml_goalnet_amd import synth
+from oracle import avm_ref
+from test_eval_golden import EVAL_CASES_SMALL, golden_buffers, head_of
+
+LEVELS = {"precision": ("fp32", "bf16", "fp16"), "head": ("regression", "classifier"), "audio": (True, False),
+          "mode": ("train", "eval"), "n": (10, 32)}
+
+
+def test_committed_cells_cover_every_three_way_combination():
+    assert 16 <= len(CELLS) <= 24 and len(set(CELLS)) == len(CELLS)
+    for c in CELLS:
+        assert all(getattr(c, f) in LEVELS[f] for f in Cell._fields), c
+    missing = []
+    for fs in itertools.combinations(Cell._fields, 3):
+        seen = {tuple(getattr(c, f) for f in fs) for c in CELLS}
+        missing += [(fs, combo) for combo in itertools.product(*(LEVELS[f] for f in fs)) if combo not in seen]
+    assert not missing, missing
+
+
+# ---- the oracle's eval path -------------------------------------------------------------------------------------------------------
+def _swapped(vis):
+    out = vis.clone()
+    out[0], out[1] = vis[1], vis[0]
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("head,audio", [("regression", True), ("regression", False), ("classifier", True), ("classifier", False)])
+def test_oracle_eval_path_equals_the_eval_restatement_bit_for_bit(head, audio, dtype):
+    """same ATen operations in the same order on the same values: exact equality of the scores, the logits and every gradient. Dropout
+    masks are passed on purpose: training=False must ignore them."""
+    n, h = 10, 40
+    params = eval_ref.classifier_params(h, audio) if head == "classifier" else synth.make_params(h, h, 30, audio)
+    vis = torch.from_numpy(synth.make_visual(n, h, h)).to(dtype)
+    aud = torch.from_numpy(synth.make_audio(n)).to(dtype) if audio else None
+    lab = torch.from_numpy(synth.make_labels(n))
+    masks = [torch.from_numpy(m).to(dtype) for m in synth.make_drop_masks(n)]
+    b = eval_ref.running_stats()
+    b0 = {k: v.clone() for k, v in b.items()}
+    pa = {k: torch.from_numpy(v.copy()).to(dtype).requires_grad_(True) for k, v in params.items()}
+    pe = {k: torch.from_numpy(v.copy()).to(dtype).requires_grad_(True) for k, v in params.items()}
+    ia, ie = {}, {}
+    out_a = avm_ref.forward(pa, b, aud, vis, masks, audio, ia, head=head, training=False)
+    out_e = eval_ref.forward(pe, b, aud, vis, audio, head, ie)
+    assert out_a.dtype == dtype and torch.equal(out_a, out_e) and torch.equal(ia["logit"], ie["logit"])
+    for i in (1, 2, 3):
+        assert torch.equal(ia[f"visbl.relu{i}"], ie[f"visbl.relu{i}"])
+    (avm_ref.ce_loss if head == "classifier" else avm_ref.mse_bcast)(out_a, lab.to(dtype)).backward()
+    eval_ref.loss_of(out_e, lab, head).backward()
+    for k in pa:
+        assert torch.equal(pa[k].grad, pe[k].grad), k
+    for k in b:
+        assert torch.equal(b[k], b0[k]), f"{k} changed under training=False"
+    # and it is not the train path in disguise
+    with torch.no_grad():
+        out_t = avm_ref.forward({k: v.detach() for k, v in pa.items()}, {k: (v.to(dtype) if v.is_floating_point() else v.clone()) for k, v in b0.items()}, aud, vis, None, audio,
+                                head=head)
+    assert (out_t - out_a).abs().max().item() > 1e-3
+
+
+@pytest.mark.parametrize("case", EVAL_CASES_SMALL)
+def test_oracle_eval_step_reproduces_the_reference_eval_goldens(case):
+    """avm_ref.train_step(training=False) against the fixtures captured from the reference under .eval(): the bounds are those of
+    tests/test_eval_golden.py::test_eval_restatement_matches_reference_goldens"""
+    g = Golden(case)
+    head = head_of(g)
+    torch.set_num_threads(8)
+    params = eval_ref.classifier_params(g.h, g.audio) if head == "classifier" else synth.make_params(g.h, g.h, 30, g.audio)
+    vis = torch.from_numpy(synth.make_visual(g.n, g.h, g.h))
+    aud = torch.from_numpy(synth.make_audio(g.n)) if g.audio else None
+    lab = torch.from_numpy(synth.make_labels(g.n))
+    b = golden_buffers(g)
+    b0 = {k: v.clone() for k, v in b.items()}
+    p = {k: torch.from_numpy(v.copy()) for k, v in params.items()}
+    inter = {}
+    loss, pred, grads = avm_ref.train_step(p, b, {}, aud, vis, lab, None, g.audio, inter, head=head, training=False)
+    g.check("s0.pred", pred, rtol=1e-6)
+    g.check("s0.loss", loss.reshape(1), rtol=1e-6)
+    g.check("s0.act.logit", inter["logit"], rtol=1e-6)
+    assert sorted(k.split("grad.", 1)[1] for k in g.keys("s0.grad.")) == sorted(p)
+    for k in g.keys("s0.grad."):
+        g.check(k, grads[k.split("grad.", 1)[1]], rtol=1e-5)
+    for k in g.keys("s0.param."):
+        g.check(k, p[k.split("param.", 1)[1]], rtol=1e-6)
+    for k in b:
+        assert torch.equal(b[k], b0[k]), f"{k} changed in eval mode"
+    p64 = {k: torch.from_numpy(v).double() for k, v in params.items()}
+    inter64 = {}
+    pred64 = avm_ref.forward(p64, b, None if aud is None else aud.double(), vis.double(), None, g.audio, inter64, head=head, training=False)
+    g.check("s0.pred", pred64, rtol=0.0, atol=2e-5)
+    g.check("s0.act.logit", inter64["logit"], rtol=0.0, atol=2e-5)
+
+
+# ---- sensitivity guard --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cell", CELLS, ids=cell_id)
+def test_cell_inputs_make_its_gradient_criterion_reject_a_frame_swap(cell):
+    """oracle vs oracle with frames 0 and 1 of the visual input swapped, everything else fixed (labels, dropout masks, statistics): the
+    cell's own criterion on conv3's and linear5's weight gradients must reject it. Measured on the oracle alone (regression head, audio):
+    train mode 0.35 - 0.5 relative L2 at both sizes, eval mode on the converged statistics 0.2 (n = 10) and 0.075 (n = 32), against
+    bf16's 2.2e-2. A cell that does not reject the swap gets other inputs or statistics, never another criterion."""
+    fx = fixture_of(cell)
+    assert fx["lab"][0] != fx["lab"][1]
+    g, pred = oracle_grads(cell, fx)
+    gs, pred_s = oracle_grads(cell, fx, vis=_swapped(fx["vis"]))
+    g64 = oracle_grads(cell, fx, dtype=torch.float64)[0] if is_fp32(cell) else None
+    # Regression head, no audio, eval mode: the broadcast MSE pairs every prediction with every label (main.py:191), there is no audio row
+    # and no dropout mask, so swapping two frames permutes the rows of a function that is symmetric in its rows: every parameter
+    # gradient is the same sum in another order, whatever the inputs. No gradient criterion can see a row mix-up in such a cell; what
+    # can is the per-row prediction, so there the cell's PREDICTION tolerance must reject the swap (and the symmetry itself is asserted).
+    symmetric = cell.head == "regression" and not cell.audio and cell.mode == "eval"
+    for name in GUARD_GRADS:
+        fig, bad = grad_verdict(cell, name, gs[name], g[name], None if g64 is None else g64[name])
+        print(f"[matrix] {cell_id(cell)} frame swap, {name}: {fig:.3e}")
+        if symmetric:
+            assert bad is None and fig < 1e-5, f"{name}: expected a row-symmetric loss, measured {fig:.3e}"
+        else:
+            assert bad is not None, f"{name}: the cell's criterion accepts a frame swap ({fig:.3e}): its inputs cannot show a row mix-up"
+        _, ok = grad_verdict(cell, name, g[name].clone(), g[name], None if g64 is None else g64[name])
+        assert ok is None
+    if symmetric:
+        d = (pred_s - pred).abs().max().item()
+        tol = 2e-5 if is_fp32(cell) else TOL16[cell.precision][2]
+        print(f"[matrix] {cell_id(cell)} frame swap, predictions: {d:.3e} (tolerance {tol})")
+        assert d > tol, "the cell's prediction tolerance accepts a frame swap"
+
+
+@pytest.mark.parametrize("cell", [c for c in CELLS if is_fp32(c) and c.head == "classifier"], ids=cell_id)
+def test_fp32_classifier_cells_leave_no_row_inside_the_class_band(cell):
+    """the classes of an fp32 cell are compared with the oracle's on EVERY row: the oracle's own top-2 score gap must exceed 4e-5 on all"""
+    fx = fixture_of(cell)
+    _, pred = oracle_grads(cell, fx)
+    top2 = pred.topk(2, dim=1).values
+    gap = (top2[:, 0] - top2[:, 1]).min().item()
+    print(f"[matrix] {cell_id(cell)}: smallest oracle top-2 score gap {gap:.2e}")
+    assert gap > CLASS_GAP
+
+
+# ---- dry run of the comparison --------------------------------------------------------------------------------------------------------
+DRY = [c for c in CELLS if (c.precision, c.mode, c.n) in {("fp32", "train", 10), ("fp32", "eval", 32), ("fp32", "eval", 10),
+                                                          ("bf16", "eval", 32), ("bf16", "train", 10), ("fp16", "eval", 10),
+                                                          ("fp16", "train", 32)}]
+
+
+def _quiet(*a):
+    pass
+
+
+@pytest.mark.parametrize("cell", DRY, ids=cell_id)
+def test_comparison_accepts_the_oracle_and_rejects_a_broken_one(cell):
+    fx = fixture_of(cell)
+    figures = compare(cell, fx, oracle_as_device(cell, fx), log=print)
+    assert figures["disagree"] == 0
+    with pytest.raises(AssertionError):
+        compare(cell, fx, oracle_as_device(cell, fx, vis=_swapped(fx["vis"])), log=_quiet)
+    if cell.mode == "eval":
+        with pytest.raises(AssertionError, match="changed under eval"):
+            compare(cell, fx, oracle_as_device(cell, fx, training=True), log=_quiet)
+
+
+def test_comparison_rejects_swapped_gradients_alone():
+    """the swap reaches compare() only through the gradients (decisions, logits and predictions are the honest ones): the gradient
+    criterion by itself turns the cell red"""
+    cell = next(c for c in CELLS if c.precision == "bf16" and c.mode == "eval" and c.n == 32 and c.head == "regression")
+    fx = fixture_of(cell)
+    dev = oracle_as_device(cell, fx)
+    dev["grads"] = dict(dev["grads"])
+    dev["grads"].update({k: oracle_grads(cell, fx, vis=_swapped(fx["vis"]))[0][k] for k in GUARD_GRADS})
+    with pytest.raises(AssertionError, match="gradient relative L2"):
+        compare(cell, fx, dev, log=_quiet)

@@ -36,6 +36,7 @@ PROTOTYPES = {
     "goalnet_conv1_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     "goalnet_conv1_wgrad_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "goalnet_conv1_wgrad": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    "goalnet_conv1_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "goalnet_stat_parts": (c_int, [c_int64]),
     "goalnet_pool_bnstats_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "goalnet_pool_bnstats_fwd_p16": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),

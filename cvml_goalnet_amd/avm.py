@@ -206,12 +206,13 @@ class AVM(nn.Module):
         self.stat_sync = None          # optional ddp.SyncStats: BatchNorm sums and the loss over all ranks' frames
         self.grad_bf16 = os.environ.get("GOALNET_DZ16", "1") != "0"   # precision="bf16": bf16 BatchNorm-output gradients (backward_device)
         self.act_bf16 = os.environ.get("GOALNET_P16", "1") != "0"     # precision="bf16": pooled activations of blocks 2, 3 stored as bf16
-        self.keep_ctx = False          # tests: keep the last train_step's saved tensors in last_ctx
+        self.keep_ctx = False          # tests: keep the last train_step's / input_gradients' saved tensors in last_ctx
         self.last_ctx = None
         self.last_used_w5b = False
         self._side_stream = None
         self._adam_stream = None
         self._dbias_pending = {}
+        self._scratch_grads = {}
         self._fused_loss, self._fused_loss_done = None, False      # train_step -> forward_device: (labels, loss, dout) for the fused MLP launch
         self._fork = _Fork(self, False)
         self.overlap_rows = int(os.environ.get("GOALNET_OVERLAP_ROWS", "64"))   # steps of <= this many frames fork their off-path work
@@ -815,11 +816,12 @@ class AVM(nn.Module):
         self.last_features = cat                    # the fusion input (N, 512 | 640): what TemporalSegmenter segments (no copy)
         return out, ctx
 
-    def _block_bwd(self, dbn, ctx, i, n, hc, wc, c):
+    def _block_bwd(self, dbn, ctx, i, n, hc, wc, c, params=True):
         """BN backward + max-pool backward + ReLU backward of block i. dbn = grad wrt the BN output (N,hc-2,wc-2,c).
-        Returns dy (N,hc,wc,c) = grad wrt the conv's pre-ReLU output; writes dgamma, dbeta, dbias into the grad arena."""
+        Returns dy (N,hc,wc,c) = grad wrt the conv's pre-ReLU output; writes dgamma, dbeta, dbias into the grad arena.
+        params=False (inputs-only backward): dgamma / dbeta, which the fused kernels cannot omit, go to scratch; no bias sums."""
         dev = self._device
-        G = self._gflat
+        G = self._gflat if params else self._gscratch
         p, idx, st = ctx[f"p{i}"], ctx[f"idx{i}"], ctx[f"st{i}"]
         npix = n * (hc - 2) * (wc - 2)
         small = self._small_bn(dbn, p, n, hc, wc, c) and not (self._half and i > 1)
@@ -840,7 +842,7 @@ class AVM(nn.Module):
             ops.bnpool_bwd(dbn, p, idx, coef3, dy, dparts, n, hc, wc, c)
             # the bias gradients' row sums feed nothing but Adam: conv3's and conv2's go out together at the end of backward (one
             # launch, side stream); conv1's is written by goalnet_conv1_wgrad from its own sums of dy
-            if i > 1:
+            if i > 1 and params:
                 self._dbias_pending[i] = dparts
             return dy
         coef3 = torch.empty(3 * c, dtype=F32, device=dev)
@@ -873,6 +875,8 @@ class AVM(nn.Module):
         else:
             dy = torch.empty(n, hc, wc, c, dtype=F32, device=dev)
             ops.bnpool_bwd(dbn, p, idx, coef3, dy, dparts, n, hc, wc, c)
+        if not params:
+            return dy
         if i == 1:
             # conv1's bias gradient is written a second time by goalnet_conv1_wgrad (on the main stream, later): keep this
             # one on the main stream too so that the order of the two writers does not depend on the schedule
@@ -881,22 +885,27 @@ class AVM(nn.Module):
             self._fork.run(lambda: ops.partials_sum(dparts, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias")), dparts)
         return dy
 
-    def _conv_block_bwd(self, i, dbn, ctx, n, hc, wc, cin, cout, wt, flipped, wait_ev, pair, out16, split_dgrad, after_block=None):
+    def _conv_block_bwd(self, i, dbn, ctx, n, hc, wc, cin, cout, wt, flipped, wait_ev, pair, out16, split_dgrad, after_block=None,
+                        params=True):
         """Backward of block i (2 or 3): from dbn = grad wrt its BatchNorm output (N,hc-2,wc-2,cout) to the grad wrt block i-1's
         BatchNorm output (N,hc,wc,cin), returned. _block_bwd, then conv{i}'s weight gradient (side stream, into the arena) and data
         gradient on the engine its forward ran on (_conv_block_fwd).
         wt: buffer for the flipped weight (csrc/layout.hip); flipped: the joint early launch fills it, and wait_ev is that launch's
         event where this block is its first reader. pair: the weight gradient goes out behind the data gradient (backward_device).
         out16: the data gradient may be stored in 16 bits; split_dgrad: it runs on split operands where the forward saved them;
-        after_block(): called between _block_bwd and the weight gradient."""
+        after_block(): called between _block_bwd and the weight gradient. params=False: the data gradient only."""
         dev, P, G, fork = self._device, self._pflat, self._gflat, self._fork
         wname, xs = f"visbl.conv{i}.weight", f"x{i - 1}s"
         flops = 2.0 * n * hc * wc * 9 * cin * cout           # the same for the weight gradient and the data gradient
-        dy = self._block_bwd(dbn, ctx, i, n, hc, wc, cout)
+        dy = self._block_bwd(dbn, ctx, i, n, hc, wc, cout, params)
         if after_block:
             after_block()
         split = not self._half and xs in ctx           # the forward ran this convolution on split operands and kept them
-        if self._half:
+        if not params:
+            wg = None
+            if split and split_dgrad:
+                dys, ady = self._split_act(f"dy{i}s", dy, None, None, n, hc, wc, cout)
+        elif self._half:
             wg, keep = (ops.conv3x3_wgrad_bf16, ctx[f"xh{i - 1}"], dy, G(wname), n, hc, wc, cin, cout), (dy,)
         elif split:
             if ctx[xs + "_gen"] != self._padgen[xs]:
@@ -912,7 +921,8 @@ class AVM(nn.Module):
             wg, keep = (ops.conv3x3_wgrad, ctx[f"p{i - 1}"], st_in[2], st_in[3], dy, G(wname), n, hc, wc, cin, cout), (dy,)
 
         def wgrad():
-            fork.run(lambda: self._timed("conv_wgrad", flops, *wg), *keep)
+            if wg is not None:
+                fork.run(lambda: self._timed("conv_wgrad", flops, *wg), *keep)
         if not pair:
             wgrad()
         if flipped:
@@ -935,16 +945,37 @@ class AVM(nn.Module):
             wgrad()                                  # behind the data gradient: runs under the next block's BatchNorm / pool passes
         return dx
 
-    def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None):
-        """dout (N,) GPU. Fills the gradient arena (every slot is overwritten). `on_bucket(k)` is called when
+    def _gscratch(self, name):
+        """inputs-only backward: where a fused kernel cannot omit a small parameter gradient (BatchNorm affine, the fused MLP, the
+        heads, AudBl's Conv1d layers) it writes here, never into the arena. The GEMM-sized gradients have no slot."""
+        s = self.spec(name)
+        if s.kind in ("ohwi", "lin5"):
+            raise GoalnetError(f"inputs-only backward asked for the gradient of {name}")
+        t = self._scratch_grads.get(name)
+        if t is None:
+            t = self._scratch_grads[name] = torch.empty(s.numel, dtype=F32, device=self._device)
+        return t
+
+    def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None, inputs=None, params=True, reduce=0):
+        """dout (N,) GPU. Fills the gradient arena (every slot is overwritten). `inputs` = (audio?, visual?): also follow the data-gradient
+        chain into the inputs and return (d_audio (N,30,B) | None, d_visual (N,3,H,W) | None) — `reduce`=1: d_visual is max_ci |.|, (N,H,W).
+        params=False: the inputs-only backward — no weight-gradient launch is issued and neither the arena nor any .grad is touched
+        (what a fused kernel cannot omit goes to _gscratch). `on_bucket(k)` is called when
         bucket k of ddp.bucket_slices() is complete (0: fusion+audbl+linear5.bias, 1: linear5.weight, 2: rest).
         `after_linear5(fork)`: called once linear5's weight gradient (side stream) and data gradient (main stream) are both
         enqueued — from there on nothing reads linear5.weight or its 16-bit copy again in this step (train_step's early Adam)."""
-        self._ensure_garena()
+        need_aud, need_vis = inputs if inputs is not None else (False, False)
+        need_aud = need_aud and self.audio_included
+        if params:
+            self._ensure_garena()
+        else:
+            self._scratch_grads = {}
         dev = self._device
         n, h, w = ctx["n"], ctx["h"], ctx["w"]
         (h1, w1), (hp1, wp1), (hp2, wp2), (hp3, wp3) = self._sizes(h, w)
-        P, G = self._pflat, self._gflat
+        P, G = self._pflat, (self._gflat if params else self._gscratch)
+        d_audio = torch.empty(n, 30, ctx["bins"], dtype=F32, device=dev) if need_aud else None
+        d_visual = None
         hs, ms = ctx["hs"], ctx["ms"]
         # small steps: weight / bias gradients and the AudBl branch run on a side stream under the dX chain (_Fork)
         fork = self._fork = _Fork(self, self._fork_ok(n) and dout.is_cuda)
@@ -987,34 +1018,36 @@ class AVM(nn.Module):
             ops.head_bwd(dout, ctx["out"], hs[4], P("fusion.12.weight"), ms[4], dz, G("fusion.12.weight"), G("fusion.12.bias"))
         for key, li in () if fused_mlp else (("9", 3), ("6", 2), ("3", 1), ("0", 0)):
             x_in, m_in = hs[li], ms[li]
-            fork.run(lambda dz=dz, x_in=x_in, key=key: ops.linear_bwd_dw(dz, x_in, G(f"fusion.{key}.weight"), db=G(f"fusion.{key}.bias")), dz)
+            if params:
+                fork.run(lambda dz=dz, x_in=x_in, key=key: ops.linear_bwd_dw(dz, x_in, G(f"fusion.{key}.weight"), db=G(f"fusion.{key}.bias")), dz)
             dprev = torch.empty(n, x_in.shape[1], dtype=F32, device=dev)
             ops.linear_bwd_dx(dz, P(f"fusion.{key}.weight"), dprev, mult=m_in)
             dz = dprev
         voff = dz.shape[1] - 512
         dz5 = dz[:, voff:]                                     # grad wrt linear5 pre-activation
 
-        if self.audio_included:
+        if self.audio_included and (params or need_aud):
             l1, l2, bins = ctx["l1"], ctx["l2"], ctx["bins"]
 
-            def audbl_bwd():                       # the whole AudBl backward hangs off dz and feeds nothing but its own gradients
+            def audbl_bwd():                       # the whole AudBl backward hangs off dz and feeds nothing but its own gradients (and d_audio)
                 dza = dz[:, :128]
                 a2f = ctx["a2"].view(n, 128 * l2)
-                ops.linear_bwd_dw(dza, a2f, G("audbl.linear3.weight"), db=G("audbl.linear3.bias"))
+                if params:
+                    ops.linear_bwd_dw(dza, a2f, G("audbl.linear3.weight"), db=G("audbl.linear3.bias"))
                 da2 = torch.empty(n, 128 * l2, dtype=F32, device=dev)
                 ops.linear_bwd_dx(dza, P("audbl.linear3.weight"), da2, mult=None)
                 da1 = torch.empty(n, 64, l1, dtype=F32, device=dev)
                 if n < 64:
                     # few frames: each Conv1d layer's backward is one launch, its ReLU backward folded into the dz load
                     ops.conv1d_bwd_small(ctx["a1"], da2, ctx["a2"], P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
-                    ops.conv1d_bwd_small(ctx["audio"], da1, ctx["a1"], P("audbl.conv1.weight"), None, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
+                    ops.conv1d_bwd_small(ctx["audio"], da1, ctx["a1"], P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
                     return
                 ops.relu_bwd(da2, a2f, da2)
                 ops.conv1d_bwd(ctx["a1"], da2, P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
                 ops.relu_bwd(da1, ctx["a1"], da1)
-                ops.conv1d_bwd(ctx["audio"], da1, P("audbl.conv1.weight"), None, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
-            fork.run(audbl_bwd, dz)
-        if not fused_mlp:
+                ops.conv1d_bwd(ctx["audio"], da1, P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
+            fork.run(audbl_bwd, dz, d_audio)
+        if not fused_mlp and params:
             fork.run(lambda: ops.colsum(dz5, G("visbl.linear5.bias")), dz)
         bucket_done(0)
 
@@ -1034,7 +1067,8 @@ class AVM(nn.Module):
                                "backward ran; call backward after each forward (as the reference's loop does)")
         if bf and ctx["bf5"]:
             dz5b = ops.cast_bf16(dz5.contiguous(), torch.empty(n, 512, dtype=self._h16, device=dev))
-            fork.run(lambda: ops.linear_bwd_dw_bf16(dz5b, ctx["xh3"].view(n, k5), G("visbl.linear5.weight")), dz5b)
+            if params:
+                fork.run(lambda: ops.linear_bwd_dw_bf16(dz5b, ctx["xh3"].view(n, k5), G("visbl.linear5.weight")), dz5b)
             bucket_done(1)
             if o16_3:
                 ops.linear_bwd_dx_bf16_o16(dz5b, ctx["w5b"], dbn3.view(n, k5))
@@ -1044,14 +1078,16 @@ class AVM(nn.Module):
                 deferred_l5.append(after_linear5) if pair else after_linear5(fork)
         elif "x3s" in ctx:
             dz5s, adz = self._split_mat(dz5, n, 512)
-            osc_w = self._osc(adz, ctx["x3s_amax"])
-            fork.run(lambda: ops.linear_bwd_dw_split(self._parts, dz5s, ctx["x3s"], G("visbl.linear5.weight"), n, k5, 512, oscale=osc_w), dz5s, osc_w)      # osc_w too: the side stream reads it (kept alive until the join)
+            osc_w = self._osc(adz, ctx["x3s_amax"]) if params else None
+            if params:
+                fork.run(lambda: ops.linear_bwd_dw_split(self._parts, dz5s, ctx["x3s"], G("visbl.linear5.weight"), n, k5, 512, oscale=osc_w), dz5s, osc_w)      # osc_w too: the side stream reads it (kept alive until the join)
             bucket_done(1)
             ops.linear_bwd_dx_split(self._parts, dz5s, ctx["w5s"], dbn3.view(n, k5), n, k5, 512, oscale=self._osc(adz, ctx["w5s_amax"]))
             if after_linear5:
                 deferred_l5.append(after_linear5) if pair else after_linear5(fork)
         else:
-            fork.run(lambda: ops.linear_bwd_dw(dz5, p3f, G("visbl.linear5.weight"), scale=st3[2], shift=st3[3], bnC=512), dz)
+            if params:
+                fork.run(lambda: ops.linear_bwd_dw(dz5, p3f, G("visbl.linear5.weight"), scale=st3[2], shift=st3[3], bnC=512), dz)
             bucket_done(1)
             ops.linear_bwd_dx(dz5, P("visbl.linear5.weight"), dbn3.view(n, k5), mult=None)
             if after_linear5:
@@ -1062,25 +1098,31 @@ class AVM(nn.Module):
         # is kept in 16 bits where BLOCK 2's fused backward reads that (_bwd16_ok of block 2's width). pair: linear5's Adam starts
         # behind _block_bwd, beside conv3's data gradient
         dbn2 = self._conv_block_bwd(3, dbn3, ctx, n, *b3, wt3, flips_early, flips_ev, pair, out16=dz16 and self._bwd16_ok(wp1),
-                                    split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5])
+                                    split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5], params=params)
         del dbn3
         # block 2 (utils.py:179-182): no wait (conv3's covered the joint flip launch); dbn1 is always fp32, its consumer is block 1's
         # fp32 path; fp16x3: the split gradient is there already (weight gradient) -> 128 x 64 tile, three segments
         dbn1 = self._conv_block_bwd(2, dbn2, ctx, n, *b2, wt2, flips_early, None, pair, out16=False,
-                                    split_dgrad=os.environ.get("GOALNET_X3_DGRAD2", "1") != "0")
+                                    split_dgrad=os.environ.get("GOALNET_X3_DGRAD2", "1") != "0", params=params)
         del dbn2
 
-        # block 1 (utils.py:174-177); conv1's input needs no gradient
-        dy1 = self._block_bwd(dbn1, ctx, 1, n, h1, w1, 64)
-        ops.conv1_wgrad(ctx["visual"], dy1, G("visbl.conv1.weight"), G("visbl.conv1.bias"), n, h, w)
+        # block 1 (utils.py:174-177); conv1's input gradient only where it was asked for (dy1 is fp32 in every precision)
+        dy1 = self._block_bwd(dbn1, ctx, 1, n, h1, w1, 64, params)
+        if params:
+            ops.conv1_wgrad(ctx["visual"], dy1, G("visbl.conv1.weight"), G("visbl.conv1.bias"), n, h, w)
+        if need_vis:
+            d_visual = ops.conv1_dgrad(dy1, P("visbl.conv1.weight"), torch.empty((n, h, w) if reduce else (n, 3, h, w), dtype=F32, device=dev),
+                                       reduce, n, h, w)
         if len(self._dbias_pending) == 2:
             d3, d2 = self._dbias_pending[3], self._dbias_pending[2]
             fork.run(lambda: ops.partials_sum2(d3, 512, G("visbl.conv3.bias"), d2, 256, G("visbl.conv2.bias")), d3, d2)
         self._dbias_pending = {}
         fork.join()                                 # every gradient is in the arena before anything downstream (Adam, all-reduce) reads it
         self._fork = _Fork(self, False)
+        self._scratch_grads = {}
         if on_bucket:
             on_bucket(2)
+        return d_audio, d_visual
 
     # ------------------------------------------------------------------------------------------
     # drop-in surface: model(audio_input, visual_input)
@@ -1103,18 +1145,69 @@ class AVM(nn.Module):
         (N,1) result is returned on the inputs' device, attached to autograd when grad mode is on."""
         aud, vis, src_dev = self._to_device_inputs(audio_input, visual_input)
         need_grad = torch.is_grad_enabled()
-        if not self._materialized:
-            # first forward materialises the Lazy parameters (shapes depend on H, W, B)
-            (_, _), _, _, (hp3, wp3) = self._sizes(vis.shape[2], vis.shape[3])
-            l2 = 0
-            if self.audio_included:
-                l2 = (((aud.shape[2] - 1) // 2 + 1) - 1) // 2 + 1
-            self._materialize(hp3 * wp3, l2)
+        self._materialize_for(aud, vis)
         if not need_grad:
             out, _ = self.forward_device(aud, vis, save=False)
             return out.view(-1, self.num_classes).to(src_dev)
         params = [getattr(*self._module_of(s.name)) for s in self._specs]
-        return _AVMFunction.apply(self, aud, vis, src_dev, *params)
+        # inputs that require grad travel through autograd as they came (any device, any float type); their gradient is returned there
+        aud_in = audio_input if (self.audio_included and audio_input.requires_grad) else None
+        vis_in = visual_input if visual_input.requires_grad else None
+        return _AVMFunction.apply(self, aud, vis, src_dev, aud_in, vis_in, *params)
+
+    def _materialize_for(self, aud, vis):
+        """first forward: materialise the Lazy parameters (shapes depend on H, W, B)"""
+        if self._materialized:
+            return
+        (_, _), _, _, (hp3, wp3) = self._sizes(vis.shape[2], vis.shape[3])
+        l2 = 0
+        if self.audio_included:
+            l2 = (((aud.shape[2] - 1) // 2 + 1) - 1) // 2 + 1
+        self._materialize(hp3 * wp3, l2)
+
+    # ------------------------------------------------------------------------------------------
+    # input gradients on the device: d(sum_i w_i out_i) / d(audio, visual) — saliency, robustness probes, input-space regularisers
+    # ------------------------------------------------------------------------------------------
+    def _input_backward(self, audio, visual, weights, reduce):
+        aud, vis, _ = self._to_device_inputs(audio, visual)
+        self._materialize_for(aud, vis)
+        out, ctx = self.forward_device(aud, vis, save=True)
+        self.last_ctx = ctx if self.keep_ctx else None
+        if weights is None:
+            dout = torch.ones(out.numel(), dtype=F32, device=self._device)
+        else:
+            if not torch.is_tensor(weights) or weights.numel() != out.numel():
+                raise RuntimeError(f"weights must be a tensor of {out.numel()} elements ((N,), or (N, C) for the classifier head)")
+            dout = weights.detach().to(device=self._device, dtype=F32).contiguous().view(-1)
+        lscale = self._loss_scale_for(ctx["n"])
+        if lscale != 1.0:                                 # fp16: scaled through the 16-bit chain, divided out of the result
+            dout = ops.scale_(dout.clone(), lscale)
+        d_aud, d_vis = self.backward_device(ctx, dout, inputs=(True, True), params=False, reduce=reduce)
+        if lscale != 1.0:
+            ops.scale_(d_vis.view(-1), 1.0 / lscale)
+            if d_aud is not None:
+                ops.scale_(d_aud.view(-1), 1.0 / lscale)
+        return d_aud, d_vis
+
+    def input_gradients(self, audio, visual, weights=None):
+        """(d_audio (N,30,B) | None, d_visual (N,3,H,W)): the gradient of sum_i weights_i * out_i wrt the inputs, as fp32 GPU tensors, with
+        no host synchronisation. `weights`: (N,) — (N, C) for the classifier head — default ones. One forward and an INPUTS-ONLY
+        backward: the data-gradient chain alone, no weight-gradient launch, and the gradient arena and every parameter's .grad are left
+        exactly as they were. Equal bit for bit to what `model(audio, visual)` followed by autograd gives for the same weights.
+        Like every forward here, a train-mode call moves the BatchNorm running statistics and draws dropout."""
+        return self._input_backward(audio, visual, weights, 0)
+
+    def saliency(self, audio, visual, weights=None, reduce="absmax"):
+        """(aud_map (N,30,B) | None, vis_map): |d_audio| and, with reduce="absmax", vis_map (N,H,W) = max over the colour channels of
+        |d_visual| (written by the data-gradient kernel itself, the (N,3,H,W) gradient is never stored); reduce="none": the raw
+        (N,3,H,W) gradient of input_gradients(). GPU tensors, no host synchronisation.
+        PER-FRAME ATTRIBUTION NEEDS model.eval(): in train mode BatchNorm normalises with the statistics of the batch, so every
+        frame's score depends on every frame's pixels and the map of frame i mixes in the other frames. A train-mode call also moves
+        the running statistics and draws dropout, as every forward here does."""
+        if reduce not in ("absmax", "none"):
+            raise ValueError("reduce must be 'absmax' or 'none'")
+        d_aud, d_vis = self._input_backward(audio, visual, weights, 1 if reduce == "absmax" else 0)
+        return (None if d_aud is None else d_aud.abs_()), d_vis
 
     # ------------------------------------------------------------------------------------------
     # device-resident fused train step (SURVEY.md §8(f)-1): forward, broadcast MSE, backward, Adam
@@ -1344,9 +1437,10 @@ class _AVMFunction(torch.autograd.Function):
     nn.Parameters (SURVEY.md §8(b) "Train step" (i)). Gradients are strided views of the gradient arena."""
 
     @staticmethod
-    def forward(ctx, model, aud, vis, src_dev, *params):
+    def forward(ctx, model, aud, vis, src_dev, aud_in, vis_in, *params):
         out, saved = model.forward_device(aud, vis, save=True)
         ctx.model, ctx.saved, ctx.src_dev = model, saved, src_dev
+        ctx.inputs_like = (aud_in, vis_in)
         return out.view(-1, model.num_classes).to(src_dev)
 
     @staticmethod
@@ -1362,10 +1456,18 @@ class _AVMFunction(torch.autograd.Function):
         lscale = model._loss_scale_for(saved["n"])
         if lscale != 1.0:                                 # fp16: scaled through the 16-bit chain, unscaled before torch sees .grad
             dout = ops.scale_(dout.clone(), lscale)
-        model.backward_device(saved, dout)
+        need = (ctx.needs_input_grad[4], ctx.needs_input_grad[5])
+        din = model.backward_device(saved, dout, inputs=need if any(need) else None)
         if lscale != 1.0:
             ops.scale_(model._garena, 1.0 / lscale)
+            for d in din:
+                if d is not None:
+                    ops.scale_(d.view(-1), 1.0 / lscale)
         model._arena_grad_scale = 1.0
         ctx.saved = None
         grads = [model._view(model._garena, s) for s in model._specs]
-        return (None, None, None, None, *grads)
+        # the inputs' gradients in the inputs' own shape, type and device (CPU leaves: one D2H copy)
+        din = [None if (d is None or not k) else d.view(like.shape).to(device=like.device, dtype=like.dtype)
+               for d, k, like in zip(din, need, ctx.inputs_like)]
+        ctx.inputs_like = None
+        return (None, None, None, None, *din, *grads)

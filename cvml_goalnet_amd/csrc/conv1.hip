@@ -1,4 +1,4 @@
-// VisBl conv1: Conv2d(3 -> 64, k3, stride 3, pad 3) + bias + ReLU, and its weight gradient.
+// VisBl conv1: Conv2d(3 -> 64, k3, stride 3, pad 3) + bias + ReLU, its weight gradient and its data gradient.
 // /root/reference/utils.py:151-152, 174-175.
 //
 // K = 27 per output: this is HBM/LDS-bound direct convolution, not matrix-core work.
@@ -375,6 +375,94 @@ __global__ __launch_bounds__(256) void conv1_wgrad_reduce_kernel(const float* __
     else if (db) db[i - CO * KP] = (float)s;
 }
 
+// Data gradient of conv1 (autograd of utils.py:174 wrt the frames): dx (NCHW) from dy = grad wrt the pre-ReLU output (NHWC).
+// Stride = kernel = 3: the windows are disjoint, so input pixel (h, w) belongs to exactly one window (oh, ow) = ((h+3)/3, (w+3)/3)
+// at tap (kh, kw) = ((h+3)%3, (w+3)%3) and
+//     dx[n][ci][h][w] = sum_co dy[n][oh][ow][co] * w[co][kh][kw][ci].
+// Every dx element is written exactly once (no atomics, no zero fill); taps that fall into the padding (window row / column 0 and
+// the trailing partial windows) write nothing. SUMMATION ORDER (fixed): one fmaf chain per element, acc = 0, co = 0, 1, ..., 63,
+// acc = fmaf(dy, w, acc) — the same chain in both output modes, so REDUCE = 1 is bit-equal to abs().amax(1) of REDUCE = 0.
+// HBM-bound by design: dy is read once (a chunk of 64 consecutive output pixels = 16 KB contiguous, float4 loads into LDS rows of
+// 65 floats: the per-pixel reads of the 64-term chain hit 32 distinct banks), dx is written once. Block = 3 waves, wave = one
+// kernel row kh, lane = one pixel of the chunk: 9 chains (kw x ci) per lane, the 9 weights of (co, kh) read as broadcast from LDS
+// ([co][kh][12]: two ds_read_b128 + one b32). The results go through LDS so that a wave stores 64 consecutive floats of one NCHW
+// row per instruction (the three kw taps of neighbouring windows are consecutive in W).
+// REDUCE = 1 stores sal[n][h][w] = max_ci |dx[n][ci][h][w]| (N, H, W) instead: a third of the write traffic, dx never materialised.
+template <int REDUCE>
+__global__ __launch_bounds__(192) void conv1_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                         float* __restrict__ out, int H, int W, int Ho, int Wo, int64_t npix) {
+    constexpr int CI = REDUCE ? 1 : 3, PX = 64, LD = 65;
+    __shared__ __attribute__((aligned(16))) float wsh[CO * 36];      // [co][kh][12]: (kw*3 + ci), three floats of padding
+    __shared__ float dys[PX * LD];
+    __shared__ float outs[3 * CI * 3 * PX];                          // [kh][ci][3*pl + kw]
+    __shared__ int pn[PX], poh[PX], pow_[PX];
+    const int tid = threadIdx.x;
+    const int kh = tid >> 6, pl = tid & 63;
+    for (int i = tid; i < CO * 36; i += 192) {
+        const int co = i / 36, r = i - co * 36, k3 = r / 12, j = r - k3 * 12;
+        wsh[i] = j < 9 ? w[co * KP + k3 * 9 + j] : 0.f;
+    }
+    const int64_t nchunks = (npix + PX - 1) / PX;
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int64_t p0 = c * PX;
+        __syncthreads();                                             // the previous chunk's readers are done
+        const float4* src = reinterpret_cast<const float4*>(dy + p0 * CO);
+        const int64_t left = (npix - p0) * (CO / 4);
+        const int lim = left < PX * (CO / 4) ? (int)left : PX * (CO / 4);
+        for (int i = tid; i < PX * (CO / 4); i += 192) {
+            const float4 v = i < lim ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            float* d = &dys[(i >> 4) * LD + (i & 15) * 4];
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        }
+        if (tid < PX) {
+            const int64_t pix = p0 + tid;
+            int n = 0, oh = -(1 << 20), ow = 0;                     // beyond the last pixel: fails the row test below
+            if (pix < npix) {
+                const int64_t t = pix / Wo;
+                ow = (int)(pix - t * Wo);
+                n = (int)(t / Ho);
+                oh = (int)(t - (int64_t)n * Ho);
+            }
+            pn[tid] = n; poh[tid] = oh; pow_[tid] = ow;
+        }
+        __syncthreads();
+        float a[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const float* dp = &dys[pl * LD];
+        const float* wk = &wsh[kh * 12];
+#pragma unroll 8
+        for (int co = 0; co < CO; ++co) {
+            const float d = dp[co];
+            const float4 w0 = *reinterpret_cast<const float4*>(wk + co * 36);
+            const float4 w1 = *reinterpret_cast<const float4*>(wk + co * 36 + 4);
+            const float w2 = wk[co * 36 + 8];
+            a[0] = fmaf(d, w0.x, a[0]); a[1] = fmaf(d, w0.y, a[1]); a[2] = fmaf(d, w0.z, a[2]);
+            a[3] = fmaf(d, w0.w, a[3]); a[4] = fmaf(d, w1.x, a[4]); a[5] = fmaf(d, w1.y, a[5]);
+            a[6] = fmaf(d, w1.z, a[6]); a[7] = fmaf(d, w1.w, a[7]); a[8] = fmaf(d, w2, a[8]);
+        }
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+            if (REDUCE) {
+                outs[kh * 3 * PX + 3 * pl + kw] = fmaxf(fmaxf(fabsf(a[kw * 3]), fabsf(a[kw * 3 + 1])), fabsf(a[kw * 3 + 2]));
+            } else {
+#pragma unroll
+                for (int ci = 0; ci < 3; ++ci) outs[(kh * 3 + ci) * 3 * PX + 3 * pl + kw] = a[kw * 3 + ci];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ci = 0; ci < CI; ++ci) {
+#pragma unroll
+            for (int pass = 0; pass < 3; ++pass) {
+                const int j = pass * PX + pl;
+                const int q = j / 3, kw = j - 3 * q;
+                const int ih = 3 * poh[q] - 3 + kh, iw = 3 * pow_[q] - 3 + kw;
+                if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W)
+                    out[(((int64_t)pn[q] * CI + ci) * H + ih) * W + iw] = outs[(kh * CI + ci) * 3 * PX + j];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -437,6 +525,26 @@ int goalnet_conv1_wgrad(const float* x_nchw, const float* dy_nhwc, float* dw_ohw
     hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3((CO * KP + CO + 15) / 16), dim3(256), 0, (hipStream_t)stream,
                        (const float*)ws, WG_PARTS, dw_ohwi, dbias);
     GN_LAUNCH_CHECK("conv1_wgrad.reduce");
+    return 0;
+}
+
+int goalnet_conv1_dgrad(const float* dy_nhwc, const float* w_ohwi, float* out, int reduce, int N, int H, int W, void* stream) {
+    GN_REQUIRE(dy_nhwc && w_ohwi && out, GOALNET_E_NULL, "conv1_dgrad: null pointer");
+    GN_REQUIRE(N > 0 && H > 0 && W > 0, GOALNET_E_SHAPE, "conv1_dgrad: non-positive dim");
+    GN_REQUIRE(reduce == 0 || reduce == 1, GOALNET_E_SHAPE, "conv1_dgrad: reduce is 0 (dx) or 1 (max_ci |dx|)");
+    const int Ho = (H + 3) / 3 + 1, Wo = (W + 3) / 3 + 1;
+    const int64_t npix = (int64_t)N * Ho * Wo;
+    GN_REQUIRE(npix < ((int64_t)1 << 31), GOALNET_E_SHAPE, "conv1_dgrad: more than 2^31 output pixels");
+    GN_REQUIRE(aligned16(dy_nhwc), GOALNET_E_ALIGN, "conv1_dgrad: dy must be 16-byte aligned");
+    int64_t blocks = (npix + 63) / 64;
+    if (blocks > 2048) blocks = 2048;
+    if (reduce)
+        hipLaunchKernelGGL(conv1_dgrad_kernel<1>, dim3((unsigned)blocks), dim3(192), 0, (hipStream_t)stream, dy_nhwc, w_ohwi, out,
+                           H, W, Ho, Wo, npix);
+    else
+        hipLaunchKernelGGL(conv1_dgrad_kernel<0>, dim3((unsigned)blocks), dim3(192), 0, (hipStream_t)stream, dy_nhwc, w_ohwi, out,
+                           H, W, Ho, Wo, npix);
+    GN_LAUNCH_CHECK("conv1_dgrad");
     return 0;
 }
 

@@ -108,6 +108,17 @@ def conv1_wgrad(x_nchw, dy, dw, db, N, H, W):
                                     N, H, W, _s()), "conv1_wgrad")
 
 
+def conv1_dgrad(dy, w, out, reduce, N, H, W):
+    """conv1's data gradient from dy (N,Ho,Wo,64): out = dx (N,3,H,W), or with reduce=1 max_ci |dx| (N,H,W); bit-equal arithmetic"""
+    _chk(dy, w, out)
+    Ho, Wo = (H + 3) // 3 + 1, (W + 3) // 3 + 1
+    _req(dy.dtype == F32 and out.dtype == F32 and dy.is_contiguous() and out.is_contiguous(), "conv1_dgrad: contiguous fp32 tensors")
+    _req(dy.numel() == N * Ho * Wo * 64 and w.numel() == 64 * 27 and out.numel() == N * (1 if reduce else 3) * H * W,
+         "conv1_dgrad: dy (N,Ho,Wo,64), w (64,3,3,3), out (N,3,H,W) or (N,H,W)")
+    check(lib().goalnet_conv1_dgrad(dy.data_ptr(), w.data_ptr(), out.data_ptr(), int(reduce), N, H, W, _s()), "conv1_dgrad")
+    return out
+
+
 def stat_parts(units):
     """rows of a partial-sum buffer for `units` independent work items (frames): min(units, STAT_PARTS)"""
     return max(1, min(int(units), STAT_PARTS))

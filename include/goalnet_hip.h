@@ -70,6 +70,11 @@ int goalnet_conv1_fwd(const float* x_nchw, const float* w_ohwi, const float* bia
 size_t goalnet_conv1_wgrad_ws_bytes(int N, int H, int W);
 int goalnet_conv1_wgrad(const float* x_nchw, const float* dy_nhwc, float* dw_ohwi, float* dbias,
                         void* ws, size_t ws_bytes, int N, int H, int W, void* stream);
+/* Data gradient of conv1 (autograd of utils.py:174 wrt visual_input) from the same dy (NHWC (N, Ho, Wo, 64), 16-byte aligned,
+ * Ho = (H+3)/3 + 1). reduce = 0: out = dx, NCHW (N, 3, H, W); reduce = 1: out = sal (N, H, W), sal[n][h][w] = max_ci |dx[n][ci][h][w]|,
+ * bit-equal to that reduction of the reduce = 0 output. Stride = kernel: every element is written exactly once (no atomics, no
+ * zero fill, deterministic); one fmaf chain per element over co = 0..63 in ascending order. fp32 only. */
+int goalnet_conv1_dgrad(const float* dy_nhwc, const float* w_ohwi, float* out, int reduce, int N, int H, int W, void* stream);
 
 /* ---- MaxPool2d(3,1,0) + train-mode BatchNorm statistics.  utils.py:153-154 (and 158-159, 163-164) */
 /* p = maxpool3x3s1(y); idx = argmax position 0..8 (first max in kh,kw scan order, as ATen), stored slice-major:

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GOALNET_LIB_PATH") or os.path.join(_HERE, "libgoalnet_hip.so")   # override: A/B builds of the kernels
 ABI_VERSION = 7
 STAT_PARTS = 1024
+ADAM_RANGES_MAX = 32      # GOALNET_ADAM_RANGES_MAX
 
 P = c_void_p  # device pointers and the stream travel as void*
 
@@ -22,6 +23,11 @@ class RowCopy(ctypes.Structure):
     """goalnet_rowcopy (include/goalnet_hip.h)"""
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_bytes", c_int64), ("nrows", c_int), ("gather", c_int), ("cursor", c_void_p),
                 ("cursor_bias", c_int64)]
+
+
+class AdamRange(ctypes.Structure):
+    """goalnet_adam_range (include/goalnet_hip.h)"""
+    _fields_ = [("begin", c_int64), ("count", c_int64), ("skipped", c_int64)]
 
 
 # name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_hip.h
@@ -132,6 +138,8 @@ PROTOTYPES = {
                                              c_int64, c_int, P]),
     "goalnet_adam_step_dev_guarded": (c_int, [P, P, P, P, c_int64, c_double, c_double, c_double, c_double, P, c_int64, c_float, P, c_int64,
                                               c_int64, c_int, P, P]),
+    "goalnet_adam_step_dev_ranges": (c_int, [P, P, P, P, ctypes.POINTER(AdamRange), c_int, c_double, c_double, c_double, c_double, P, c_float,
+                                             P, c_int64, c_int64, c_int, P, P]),
     "goalnet_scale": (c_int, [P, c_int64, c_float, P]),
     "goalnet_grad_finite_check": (c_int, [P, c_int64, P, c_int64, P, P, P]),
     "goalnet_counters_add4": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P]),

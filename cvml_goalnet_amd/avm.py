@@ -45,11 +45,25 @@ BN_MOMENTUM = 0.1
 _ALIGN = 64  # arena slots are multiples of 64 floats (256 B)
 
 
-class _Holder(nn.Module):
+class _LazyFlags:
+    """`module.requires_grad_(flag)` that also works before the first forward: torch refuses the tensor method on a Lazy
+    (uninitialised) parameter, but the flag is a plain attribute and stays with the nn.Parameter when AVM._materialize fixes its shape."""
+
+    def requires_grad_(self, requires_grad: bool = True):
+        for p in self.parameters():
+            p.requires_grad = requires_grad
+        return self
+
+
+class _Holder(_LazyFlags, nn.Module):
     """A sub-module that only owns parameters/buffers (keeps the reference's state_dict key prefixes)."""
 
     def forward(self, *a, **k):  # pragma: no cover
         raise GoalnetError("sub-modules of the MI355X AVM are parameter holders; call the AVM itself")
+
+
+class _Layers(_LazyFlags, nn.ModuleDict):
+    pass
 
 
 def _mk_layer(bias=True, bn_channels=0):
@@ -122,7 +136,26 @@ class _Spec:
         self.offset = 0
 
 
-class AVM(nn.Module):
+def trainable_ranges(specs, frozen, skipped):
+    """[(begin, count, skipped)]: the arena ranges the fused Adam updates when the tensors named in `frozen` sit the step out
+    (ops.adam_step_dev_ranges). Trainable tensors in neighbouring slots merge into one range — the slot padding between them included,
+    which holds zeros in all four arenas and stays zero under Adam — as long as they sat out the same number of optimizer steps
+    (`skipped`: name -> count, missing = 0), because a range has one bias-correction count. Pure: the host tests call it."""
+    out, slot_end = [], None
+    for s in sorted(specs, key=lambda s: s.offset):
+        if s.name in frozen:
+            slot_end = None
+            continue
+        k = int(skipped.get(s.name, 0))
+        if out and slot_end == s.offset and out[-1][2] == k:
+            out[-1] = (out[-1][0], s.offset + s.numel - out[-1][0], k)
+        else:
+            out.append((s.offset, s.numel, k))
+        slot_end = s.offset + (s.numel + _ALIGN - 1) // _ALIGN * _ALIGN
+    return out
+
+
+class AVM(_LazyFlags, nn.Module):
     def __init__(self, audio_included, device=None, seed: Optional[int] = None, precision: str = "fp32", head: str = "regression",
                  num_classes: int = 5):
         """`seed`: seed of the counter-based dropout stream. None (default) draws it from the torch RNG at construction, so
@@ -180,7 +213,7 @@ class AVM(nn.Module):
             self.audbl.conv1 = _mk_layer()
             self.audbl.conv2 = _mk_layer()
             self.audbl.linear3 = _mk_layer()
-        self.fusion = nn.ModuleDict({k: _mk_layer() for k in ("0", "3", "6", "9", "12")})   # utils.py:242-256
+        self.fusion = _Layers({k: _mk_layer() for k in ("0", "3", "6", "9", "12")})   # utils.py:242-256
 
         # dropout (utils.py:170, 245-254): "device" = counter-based masks (synth.make_drop_masks formula),
         # "off" = p := 0, "given" = masks supplied through set_dropout_masks() (parity tests)
@@ -195,6 +228,11 @@ class AVM(nn.Module):
         self._hw3 = self._l2 = None
         self._adam_t = 0
         self._adam_segs = None
+        # fine-tuning: a tensor whose nn.Parameter has requires_grad=False is FROZEN — no gradient, no update, and
+        # the optimizer steps it sits out are counted per tensor (torch.optim.Adam keeps a step count per parameter)
+        self._sat_out = {}                 # name -> optimizer steps the tensor sat out so far (missing = 0)
+        self._bwd_frozen = frozenset()     # the frozen set the last parameter backward ran under: what the next optimizer step skips
+        self._fp16_frozen = None           # precision="fp16": the frozen set of the first optimizer step (it may not change afterwards)
         self._arena_grad_scale = 1.0       # the gradient arena currently holds this factor x gradient (fp16 train_step)
         self._w5b, self._w5b_version = None, None      # bf16 shadow of visbl.linear5.weight and the version stamps it matches
         self._load_count = 0                           # bumped by load_state_dict (its layout kernels write the arena directly)
@@ -375,6 +413,43 @@ class AVM(nn.Module):
     def _ensure_garena(self):
         if self._garena is None:
             self._garena = torch.zeros(self._arena_numel, dtype=F32, device=self._device)
+
+    def _frozen_names(self):
+        """names of the parameter tensors with requires_grad=False (the flags live on the nn.Parameters, also while they are Lazy)"""
+        return frozenset(k for k, p in self.named_parameters() if not p.requires_grad)
+
+    def _check_freeze(self, frozen):
+        if frozen and (self.grad_sync is not None or self.stat_sync is not None):
+            raise GoalnetError("freezing under DDP is not built: every parameter must have requires_grad=True while a grad_sync / "
+                               "stat_sync is attached (bucket layouts and sharding are laid out for the whole arena)")
+
+    def _plain_step(self, frozen):
+        """every tensor trains under the global step count: today's single pass over the arena"""
+        return not frozen and not any(self._sat_out.values())
+
+    def trainable_signature(self):
+        """what a captured step bakes in about the trainable set: () while every tensor trains under the global step count, else the
+        (begin, count, skipped) of every range of the fused Adam (before the Lazy shapes are fixed: the frozen names)"""
+        frozen = self._frozen_names()
+        if self._plain_step(frozen):
+            return ()
+        if not self._materialized:
+            return tuple(sorted(frozen))
+        return tuple(trainable_ranges(self._specs, frozen, self._sat_out))
+
+    def _count_sat_out(self, frozen):
+        for k in frozen:
+            self._sat_out[k] = self._sat_out.get(k, 0) + 1
+
+    def _exact_runs(self, names):
+        """[(lo, hi)] of the named tensors, neighbours merged only where no slot padding lies between them"""
+        runs = []
+        for s in sorted((self.spec(k) for k in names), key=lambda s: s.offset):
+            if runs and runs[-1][1] == s.offset:
+                runs[-1] = (runs[-1][0], s.offset + s.numel)
+            else:
+                runs.append((s.offset, s.offset + s.numel))
+        return runs
 
     # ------------------------------------------------------------------------------------------
     # state_dict interchange in the reference's torch-native layouts (main.py:66, 263, 282, 326)
@@ -816,12 +891,13 @@ class AVM(nn.Module):
         self.last_features = cat                    # the fusion input (N, 512 | 640): what TemporalSegmenter segments (no copy)
         return out, ctx
 
-    def _block_bwd(self, dbn, ctx, i, n, hc, wc, c, params=True):
+    def _block_bwd(self, dbn, ctx, i, n, hc, wc, c, G=None, bias=True):
         """BN backward + max-pool backward + ReLU backward of block i. dbn = grad wrt the BN output (N,hc-2,wc-2,c).
-        Returns dy (N,hc,wc,c) = grad wrt the conv's pre-ReLU output; writes dgamma, dbeta, dbias into the grad arena.
-        params=False (inputs-only backward): dgamma / dbeta, which the fused kernels cannot omit, go to scratch; no bias sums."""
+        Returns dy (N,hc,wc,c) = grad wrt the conv's pre-ReLU output; writes dgamma, dbeta, dbias where G(name) says (the grad arena;
+        scratch for a frozen tensor and in the inputs-only backward: the fused kernels cannot omit dgamma / dbeta).
+        bias=False: conv{i}.bias is not trained — no bias sums."""
         dev = self._device
-        G = self._gflat if params else self._gscratch
+        G = G or self._gflat
         p, idx, st = ctx[f"p{i}"], ctx[f"idx{i}"], ctx[f"st{i}"]
         npix = n * (hc - 2) * (wc - 2)
         small = self._small_bn(dbn, p, n, hc, wc, c) and not (self._half and i > 1)
@@ -842,8 +918,8 @@ class AVM(nn.Module):
             ops.bnpool_bwd(dbn, p, idx, coef3, dy, dparts, n, hc, wc, c)
             # the bias gradients' row sums feed nothing but Adam: conv3's and conv2's go out together at the end of backward (one
             # launch, side stream); conv1's is written by goalnet_conv1_wgrad from its own sums of dy
-            if i > 1 and params:
-                self._dbias_pending[i] = dparts
+            if i > 1 and bias:
+                self._dbias_pending[i] = (dparts, c)
             return dy
         coef3 = torch.empty(3 * c, dtype=F32, device=dev)
         partials = torch.empty(ops.stat_parts(npix // 64) * 2 * c, dtype=torch.float64, device=dev)
@@ -875,7 +951,7 @@ class AVM(nn.Module):
         else:
             dy = torch.empty(n, hc, wc, c, dtype=F32, device=dev)
             ops.bnpool_bwd(dbn, p, idx, coef3, dy, dparts, n, hc, wc, c)
-        if not params:
+        if not bias:
             return dy
         if i == 1:
             # conv1's bias gradient is written a second time by goalnet_conv1_wgrad (on the main stream, later): keep this
@@ -886,24 +962,26 @@ class AVM(nn.Module):
         return dy
 
     def _conv_block_bwd(self, i, dbn, ctx, n, hc, wc, cin, cout, wt, flipped, wait_ev, pair, out16, split_dgrad, after_block=None,
-                        params=True):
+                        G=None, train=(True, True), dgrad=True):
         """Backward of block i (2 or 3): from dbn = grad wrt its BatchNorm output (N,hc-2,wc-2,cout) to the grad wrt block i-1's
         BatchNorm output (N,hc,wc,cin), returned. _block_bwd, then conv{i}'s weight gradient (side stream, into the arena) and data
         gradient on the engine its forward ran on (_conv_block_fwd).
         wt: buffer for the flipped weight (csrc/layout.hip); flipped: the joint early launch fills it, and wait_ev is that launch's
         event where this block is its first reader. pair: the weight gradient goes out behind the data gradient (backward_device).
         out16: the data gradient may be stored in 16 bits; split_dgrad: it runs on split operands where the forward saved them;
-        after_block(): called between _block_bwd and the weight gradient. params=False: the data gradient only."""
-        dev, P, G, fork = self._device, self._pflat, self._gflat, self._fork
+        after_block(): called between _block_bwd and the weight gradient. train = (conv{i}.weight, conv{i}.bias) are trained: no
+        weight-gradient launch / no bias sums otherwise; dgrad=False: nothing beneath this block wants a gradient — no data gradient,
+        None is returned. G: where a parameter gradient goes (_block_bwd)."""
+        dev, P, G, fork = self._device, self._pflat, G or self._gflat, self._fork
         wname, xs = f"visbl.conv{i}.weight", f"x{i - 1}s"
         flops = 2.0 * n * hc * wc * 9 * cin * cout           # the same for the weight gradient and the data gradient
-        dy = self._block_bwd(dbn, ctx, i, n, hc, wc, cout, params)
+        dy = self._block_bwd(dbn, ctx, i, n, hc, wc, cout, G, train[1])
         if after_block:
             after_block()
         split = not self._half and xs in ctx           # the forward ran this convolution on split operands and kept them
-        if not params:
+        if not train[0]:
             wg = None
-            if split and split_dgrad:
+            if split and split_dgrad and dgrad:
                 dys, ady = self._split_act(f"dy{i}s", dy, None, None, n, hc, wc, cout)
         elif self._half:
             wg, keep = (ops.conv3x3_wgrad_bf16, ctx[f"xh{i - 1}"], dy, G(wname), n, hc, wc, cin, cout), (dy,)
@@ -925,6 +1003,10 @@ class AVM(nn.Module):
                 fork.run(lambda: self._timed("conv_wgrad", flops, *wg), *keep)
         if not pair:
             wgrad()
+        if not dgrad:
+            if pair:
+                wgrad()
+            return None
         if flipped:
             fork.wait(wait_ev)                       # None: an earlier block's wait covered the joint flip launch
         else:
@@ -949,31 +1031,56 @@ class AVM(nn.Module):
         """inputs-only backward: where a fused kernel cannot omit a small parameter gradient (BatchNorm affine, the fused MLP, the
         heads, AudBl's Conv1d layers) it writes here, never into the arena. The GEMM-sized gradients have no slot."""
         s = self.spec(name)
-        if s.kind in ("ohwi", "lin5"):
-            raise GoalnetError(f"inputs-only backward asked for the gradient of {name}")
+        if s.kind in ("ohwi", "lin5") and name != "visbl.conv1.weight":      # conv1's comes from the launch that sums conv1.bias's
+            raise GoalnetError(f"a backward that does not train {name} asked for its gradient")
         t = self._scratch_grads.get(name)
         if t is None:
             t = self._scratch_grads[name] = torch.empty(s.numel, dtype=F32, device=self._device)
         return t
 
-    def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None, inputs=None, params=True, reduce=0):
-        """dout (N,) GPU. Fills the gradient arena (every slot is overwritten). `inputs` = (audio?, visual?): also follow the data-gradient
-        chain into the inputs and return (d_audio (N,30,B) | None, d_visual (N,3,H,W) | None) — `reduce`=1: d_visual is max_ci |.|, (N,H,W).
-        params=False: the inputs-only backward — no weight-gradient launch is issued and neither the arena nor any .grad is touched
-        (what a fused kernel cannot omit goes to _gscratch). `on_bucket(k)` is called when
+    def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None, inputs=None, params=True, reduce=0, frozen=None):
+        """dout (N,) GPU. Fills the gradient arena (the slot of every TRAINABLE tensor is overwritten). `inputs` = (audio?, visual?): also
+        follow the data-gradient chain into the inputs and return (d_audio (N,30,B) | None, d_visual (N,3,H,W) | None) — `reduce`=1:
+        d_visual is max_ci |.|, (N,H,W).
+        `frozen`: names of the tensors that are not trained (default: those whose nn.Parameter has requires_grad=False, read here, at
+        the start of the backward). A frozen tensor gets no gradient: a launch whose only outputs are frozen gradients is not issued,
+        what a fused kernel cannot omit goes to _gscratch, and each branch of the data-gradient chain stops below its lowest trainable
+        tensor unless an input gradient is asked for. Gradients of trainable tensors are the same bits either way.
+        params=False: the inputs-only backward — every tensor counts as frozen, and neither the arena nor any .grad is touched.
+        `on_bucket(k)` is called when
         bucket k of ddp.bucket_slices() is complete (0: fusion+audbl+linear5.bias, 1: linear5.weight, 2: rest).
         `after_linear5(fork)`: called once linear5's weight gradient (side stream) and data gradient (main stream) are both
         enqueued — from there on nothing reads linear5.weight or its 16-bit copy again in this step (train_step's early Adam)."""
         need_aud, need_vis = inputs if inputs is not None else (False, False)
         need_aud = need_aud and self.audio_included
+        self._scratch_grads = {}
         if params:
             self._ensure_garena()
+            frozen = self._frozen_names() if frozen is None else frozenset(frozen)
+            self._check_freeze(frozen)
+            self._bwd_frozen = frozen
+            train = frozenset(s.name for s in self._specs) - frozen
         else:
-            self._scratch_grads = {}
+            train = frozenset()
+        T = train.__contains__
+
+        def G(name):
+            return self._gflat(name) if name in train else self._gscratch(name)
+
+        def any_T(*layers):
+            return any(f"{layer}.{leaf}" in train for layer in layers for leaf in ("weight", "bias"))
         dev = self._device
         n, h, w = ctx["n"], ctx["h"], ctx["w"]
         (h1, w1), (hp1, wp1), (hp2, wp2), (hp3, wp3) = self._sizes(h, w)
-        P, G = self._pflat, (self._gflat if params else self._gscratch)
+        P = self._pflat
+        # what each stage of the VisBl chain is needed for: block i's BatchNorm / pool / ReLU backward (b_i) feeds its own parameters and
+        # everything beneath; conv_i's data gradient (d_i) feeds block i-1
+        need_b1 = need_vis or any_T("visbl.bnorm1", "visbl.conv1")
+        need_b2 = need_b1 or any_T("visbl.bnorm2", "visbl.conv2")          # = conv3's data gradient is needed
+        need_b3 = need_b2 or any_T("visbl.bnorm3", "visbl.conv3")          # = linear5's data gradient is needed
+        train_w5 = T("visbl.linear5.weight")
+        need_audbl = self.audio_included and (need_aud or any_T("audbl.linear3", "audbl.conv2", "audbl.conv1"))
+        need_cat = need_audbl or need_b3 or train_w5 or T("visbl.linear5.bias")      # the gradient behind `cat` is needed
         d_audio = torch.empty(n, 30, ctx["bins"], dtype=F32, device=dev) if need_aud else None
         d_visual = None
         hs, ms = ctx["hs"], ctx["ms"]
@@ -995,11 +1102,12 @@ class AVM(nn.Module):
                 on_bucket(k)
 
         # the data gradients of conv3 / conv2 read the weights flipped (csrc/layout.hip); the flips depend on nothing but the
-        # weights, so in a small step both go out FIRST, in one launch on the side stream, off the dX chain
-        wt3 = torch.empty(512 * 9 * 256, dtype=F32, device=dev)
-        wt2 = torch.empty(256 * 9 * 64, dtype=F32, device=dev)
+        # weights, so in a small step both go out FIRST, in one launch on the side stream, off the dX chain (where both data gradients
+        # run; where only conv3's does, its block flips its own weight)
+        wt3 = torch.empty(512 * 9 * 256, dtype=F32, device=dev) if need_b2 else None
+        wt2 = torch.empty(256 * 9 * 64, dtype=F32, device=dev) if need_b1 else None
         flips_ev = None
-        flips_early = fork.enabled
+        flips_early = fork.enabled and need_b1
         if flips_early:
             _, flips_ev = fork.run_marked(lambda: ops.conv3x3_weight_flip2(P("visbl.conv3.weight"), wt3, 512, 256,
                                                                           P("visbl.conv2.weight"), wt2, 256, 64), wt3, wt2)
@@ -1016,106 +1124,138 @@ class AVM(nn.Module):
                              G("fusion.12.weight"), G("fusion.12.bias"))
         else:
             ops.head_bwd(dout, ctx["out"], hs[4], P("fusion.12.weight"), ms[4], dz, G("fusion.12.weight"), G("fusion.12.bias"))
-        for key, li in () if fused_mlp else (("9", 3), ("6", 2), ("3", 1), ("0", 0)):
+        chain = True                               # dz is still wanted by something beneath
+        lower = ("fusion.6", "fusion.3", "fusion.0")
+        for k, (key, li) in enumerate(() if fused_mlp else (("9", 3), ("6", 2), ("3", 1), ("0", 0))):
             x_in, m_in = hs[li], ms[li]
-            if params:
+            if any_T(f"fusion.{key}"):
                 fork.run(lambda dz=dz, x_in=x_in, key=key: ops.linear_bwd_dw(dz, x_in, G(f"fusion.{key}.weight"), db=G(f"fusion.{key}.bias")), dz)
+            if not (need_cat or any_T(*lower[k:])):
+                chain = False                      # nothing trainable beneath this layer: the chain ends here
+                break
             dprev = torch.empty(n, x_in.shape[1], dtype=F32, device=dev)
             ops.linear_bwd_dx(dz, P(f"fusion.{key}.weight"), dprev, mult=m_in)
             dz = dprev
+        chain = chain and need_cat
         voff = dz.shape[1] - 512
-        dz5 = dz[:, voff:]                                     # grad wrt linear5 pre-activation
+        dz5 = dz[:, voff:]                                     # grad wrt linear5 pre-activation (where the chain got this far)
 
-        if self.audio_included and (params or need_aud):
+        if chain and need_audbl:
             l1, l2, bins = ctx["l1"], ctx["l2"], ctx["bins"]
+            conv_a1 = need_aud or any_T("audbl.conv1")                 # conv1's backward runs
+            conv_a2 = conv_a1 or any_T("audbl.conv2")                  # conv2's backward (and linear3's data gradient) runs
 
             def audbl_bwd():                       # the whole AudBl backward hangs off dz and feeds nothing but its own gradients (and d_audio)
                 dza = dz[:, :128]
                 a2f = ctx["a2"].view(n, 128 * l2)
-                if params:
+                if any_T("audbl.linear3"):
                     ops.linear_bwd_dw(dza, a2f, G("audbl.linear3.weight"), db=G("audbl.linear3.bias"))
+                if not conv_a2:
+                    return
                 da2 = torch.empty(n, 128 * l2, dtype=F32, device=dev)
                 ops.linear_bwd_dx(dza, P("audbl.linear3.weight"), da2, mult=None)
-                da1 = torch.empty(n, 64, l1, dtype=F32, device=dev)
+                da1 = torch.empty(n, 64, l1, dtype=F32, device=dev) if conv_a1 else None
                 if n < 64:
                     # few frames: each Conv1d layer's backward is one launch, its ReLU backward folded into the dz load
                     ops.conv1d_bwd_small(ctx["a1"], da2, ctx["a2"], P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
-                    ops.conv1d_bwd_small(ctx["audio"], da1, ctx["a1"], P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
+                    if conv_a1:
+                        ops.conv1d_bwd_small(ctx["audio"], da1, ctx["a1"], P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
                     return
                 ops.relu_bwd(da2, a2f, da2)
                 ops.conv1d_bwd(ctx["a1"], da2, P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
-                ops.relu_bwd(da1, ctx["a1"], da1)
-                ops.conv1d_bwd(ctx["audio"], da1, P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
+                if conv_a1:
+                    ops.relu_bwd(da1, ctx["a1"], da1)
+                    ops.conv1d_bwd(ctx["audio"], da1, P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
             fork.run(audbl_bwd, dz, d_audio)
-        if not fused_mlp and params:
+        if chain and not fused_mlp and T("visbl.linear5.bias"):
             fork.run(lambda: ops.colsum(dz5, G("visbl.linear5.bias")), dz)
         bucket_done(0)
 
         # linear5 (utils.py:191): dW straight into the arena, dX = grad wrt bnorm3's output
         k5 = 512 * hp3 * wp3
-        p3f = ctx["p3"].view(n, k5)
-        st3 = ctx["st3"]
         bf = self._half
         # precision="bf16" / "fp16": where the 256 x 256 tile serves the data-gradient GEMM, the gradient wrt a BatchNorm output is
         # stored as bf16 (fp32 accumulators rounded once, at the store): its only readers are the two HBM-bound passes of
         # _block_bwd, and the GEMMs behind them consume bf16 anyway
         dz16 = bf and self.grad_bf16
-        o16_3 = dz16 and ctx["bf5"] and self._bwd16_ok(wp2) and ops.linear_bwd_dx_bf16_o16_ok(n, k5, 512)
-        dbn3 = torch.empty(n, hp3, wp3, 512, dtype=self._h16 if o16_3 else F32, device=dev)
         if bf and ctx["padgen"] != (self._padgen["x1"], self._padgen["x2"]):
             raise RuntimeError("precision='bf16': a second training-mode forward overwrote the saved bf16 operands before "
                                "backward ran; call backward after each forward (as the reference's loop does)")
-        if bf and ctx["bf5"]:
-            dz5b = ops.cast_bf16(dz5.contiguous(), torch.empty(n, 512, dtype=self._h16, device=dev))
-            if params:
-                fork.run(lambda: ops.linear_bwd_dw_bf16(dz5b, ctx["xh3"].view(n, k5), G("visbl.linear5.weight")), dz5b)
-            bucket_done(1)
-            if o16_3:
-                ops.linear_bwd_dx_bf16_o16(dz5b, ctx["w5b"], dbn3.view(n, k5))
+        dbn3 = None
+        if chain and (train_w5 or need_b3):
+            p3f = ctx["p3"].view(n, k5)
+            st3 = ctx["st3"]
+            o16_3 = dz16 and ctx["bf5"] and self._bwd16_ok(wp2) and ops.linear_bwd_dx_bf16_o16_ok(n, k5, 512)
+            if need_b3:
+                dbn3 = torch.empty(n, hp3, wp3, 512, dtype=self._h16 if o16_3 else F32, device=dev)
+
+            def linear5_done():
+                if after_linear5 and train_w5:
+                    # pair: linear5's Adam starts behind block 3's _block_bwd, beside conv3's data gradient (where that block runs)
+                    deferred_l5.append(after_linear5) if (pair and need_b3) else after_linear5(fork)
+            if bf and ctx["bf5"]:
+                dz5b = ops.cast_bf16(dz5.contiguous(), torch.empty(n, 512, dtype=self._h16, device=dev))
+                if train_w5:
+                    fork.run(lambda: ops.linear_bwd_dw_bf16(dz5b, ctx["xh3"].view(n, k5), G("visbl.linear5.weight")), dz5b)
+                bucket_done(1)
+                if not need_b3:
+                    pass
+                elif o16_3:
+                    ops.linear_bwd_dx_bf16_o16(dz5b, ctx["w5b"], dbn3.view(n, k5))
+                else:
+                    ops.linear_bwd_dx_bf16(dz5b, ctx["w5b"], dbn3.view(n, k5), mult=None)
+            elif "x3s" in ctx:
+                dz5s, adz = self._split_mat(dz5, n, 512)
+                if train_w5:
+                    osc_w = self._osc(adz, ctx["x3s_amax"])
+                    fork.run(lambda: ops.linear_bwd_dw_split(self._parts, dz5s, ctx["x3s"], G("visbl.linear5.weight"), n, k5, 512, oscale=osc_w), dz5s, osc_w)      # osc_w too: the side stream reads it (kept alive until the join)
+                bucket_done(1)
+                if need_b3:
+                    ops.linear_bwd_dx_split(self._parts, dz5s, ctx["w5s"], dbn3.view(n, k5), n, k5, 512, oscale=self._osc(adz, ctx["w5s_amax"]))
             else:
-                ops.linear_bwd_dx_bf16(dz5b, ctx["w5b"], dbn3.view(n, k5), mult=None)
-            if after_linear5:
-                deferred_l5.append(after_linear5) if pair else after_linear5(fork)
-        elif "x3s" in ctx:
-            dz5s, adz = self._split_mat(dz5, n, 512)
-            osc_w = self._osc(adz, ctx["x3s_amax"]) if params else None
-            if params:
-                fork.run(lambda: ops.linear_bwd_dw_split(self._parts, dz5s, ctx["x3s"], G("visbl.linear5.weight"), n, k5, 512, oscale=osc_w), dz5s, osc_w)      # osc_w too: the side stream reads it (kept alive until the join)
-            bucket_done(1)
-            ops.linear_bwd_dx_split(self._parts, dz5s, ctx["w5s"], dbn3.view(n, k5), n, k5, 512, oscale=self._osc(adz, ctx["w5s_amax"]))
-            if after_linear5:
-                deferred_l5.append(after_linear5) if pair else after_linear5(fork)
+                if train_w5:
+                    fork.run(lambda: ops.linear_bwd_dw(dz5, p3f, G("visbl.linear5.weight"), scale=st3[2], shift=st3[3], bnC=512), dz)
+                bucket_done(1)
+                if need_b3:
+                    ops.linear_bwd_dx(dz5, P("visbl.linear5.weight"), dbn3.view(n, k5), mult=None)
+            linear5_done()
         else:
-            if params:
-                fork.run(lambda: ops.linear_bwd_dw(dz5, p3f, G("visbl.linear5.weight"), scale=st3[2], shift=st3[3], bnC=512), dz)
             bucket_done(1)
-            ops.linear_bwd_dx(dz5, P("visbl.linear5.weight"), dbn3.view(n, k5), mult=None)
-            if after_linear5:
-                deferred_l5.append(after_linear5) if pair else after_linear5(fork)
 
         b2, b3 = (hp1, wp1, 64, 256), (hp2, wp2, 256, 512)          # (hc, wc, cin, cout) of the two 3 x 3 blocks
-        # block 3 (utils.py:184-187): the first reader of the flipped weights (waits for the joint early launch). Its data gradient
-        # is kept in 16 bits where BLOCK 2's fused backward reads that (_bwd16_ok of block 2's width). pair: linear5's Adam starts
-        # behind _block_bwd, beside conv3's data gradient
-        dbn2 = self._conv_block_bwd(3, dbn3, ctx, n, *b3, wt3, flips_early, flips_ev, pair, out16=dz16 and self._bwd16_ok(wp1),
-                                    split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5], params=params)
+        dbn2 = dbn1 = None
+        if dbn3 is not None:
+            # block 3 (utils.py:184-187): the first reader of the flipped weights (waits for the joint early launch). Its data gradient
+            # is kept in 16 bits where BLOCK 2's fused backward reads that (_bwd16_ok of block 2's width). pair: linear5's Adam starts
+            # behind _block_bwd, beside conv3's data gradient
+            dbn2 = self._conv_block_bwd(3, dbn3, ctx, n, *b3, wt3, flips_early, flips_ev, pair, out16=dz16 and self._bwd16_ok(wp1),
+                                        split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5], G=G,
+                                        train=(T("visbl.conv3.weight"), T("visbl.conv3.bias")), dgrad=need_b2)
         del dbn3
-        # block 2 (utils.py:179-182): no wait (conv3's covered the joint flip launch); dbn1 is always fp32, its consumer is block 1's
-        # fp32 path; fp16x3: the split gradient is there already (weight gradient) -> 128 x 64 tile, three segments
-        dbn1 = self._conv_block_bwd(2, dbn2, ctx, n, *b2, wt2, flips_early, None, pair, out16=False,
-                                    split_dgrad=os.environ.get("GOALNET_X3_DGRAD2", "1") != "0", params=params)
+        if dbn2 is not None:
+            # block 2 (utils.py:179-182): no wait (conv3's covered the joint flip launch); dbn1 is always fp32, its consumer is block 1's
+            # fp32 path; fp16x3: the split gradient is there already (weight gradient) -> 128 x 64 tile, three segments
+            dbn1 = self._conv_block_bwd(2, dbn2, ctx, n, *b2, wt2, flips_early, None, pair, out16=False,
+                                        split_dgrad=os.environ.get("GOALNET_X3_DGRAD2", "1") != "0", G=G,
+                                        train=(T("visbl.conv2.weight"), T("visbl.conv2.bias")), dgrad=need_b1)
         del dbn2
 
-        # block 1 (utils.py:174-177); conv1's input gradient only where it was asked for (dy1 is fp32 in every precision)
-        dy1 = self._block_bwd(dbn1, ctx, 1, n, h1, w1, 64, params)
-        if params:
-            ops.conv1_wgrad(ctx["visual"], dy1, G("visbl.conv1.weight"), G("visbl.conv1.bias"), n, h, w)
-        if need_vis:
-            d_visual = ops.conv1_dgrad(dy1, P("visbl.conv1.weight"), torch.empty((n, h, w) if reduce else (n, 3, h, w), dtype=F32, device=dev),
-                                       reduce, n, h, w)
+        if dbn1 is not None:
+            # block 1 (utils.py:174-177); conv1's input gradient only where it was asked for (dy1 is fp32 in every precision)
+            train_c1 = any_T("visbl.conv1")
+            dy1 = self._block_bwd(dbn1, ctx, 1, n, h1, w1, 64, G, T("visbl.conv1.bias"))
+            if train_c1:
+                ops.conv1_wgrad(ctx["visual"], dy1, G("visbl.conv1.weight"), G("visbl.conv1.bias"), n, h, w)
+            if need_vis:
+                d_visual = ops.conv1_dgrad(dy1, P("visbl.conv1.weight"), torch.empty((n, h, w) if reduce else (n, 3, h, w), dtype=F32, device=dev),
+                                           reduce, n, h, w)
         if len(self._dbias_pending) == 2:
-            d3, d2 = self._dbias_pending[3], self._dbias_pending[2]
+            (d3, _), (d2, _) = self._dbias_pending[3], self._dbias_pending[2]
             fork.run(lambda: ops.partials_sum2(d3, 512, G("visbl.conv3.bias"), d2, 256, G("visbl.conv2.bias")), d3, d2)
+        else:
+            # one of the two blocks did not run or does not train its bias: the same column sums, one array
+            for i, (dp, c) in self._dbias_pending.items():
+                fork.run(lambda i=i, dp=dp, c=c: ops.partials_sum(dp, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias")), dp)
         self._dbias_pending = {}
         fork.join()                                 # every gradient is in the arena before anything downstream (Adam, all-reduce) reads it
         self._fork = _Fork(self, False)
@@ -1150,6 +1290,7 @@ class AVM(nn.Module):
             out, _ = self.forward_device(aud, vis, save=False)
             return out.view(-1, self.num_classes).to(src_dev)
         params = [getattr(*self._module_of(s.name)) for s in self._specs]
+        self._check_freeze([s.name for s, prm in zip(self._specs, params) if not prm.requires_grad])
         # inputs that require grad travel through autograd as they came (any device, any float type); their gradient is returned there
         aud_in = audio_input if (self.audio_included and audio_input.requires_grad) else None
         vis_in = visual_input if visual_input.requires_grad else None
@@ -1217,6 +1358,9 @@ class AVM(nn.Module):
         `_loop_tick`: (frames, sub-batches) the caller's loop counters advance by (loop.VideoTrainer); `_scatter(loss, pred)` -> row-copy
         segments (ops.rows_copy_batch form, cursors as they stand BEFORE the tick) that the step's last launch writes before it advances
         the counters (the per-video predictions / losses arrays of loop.VideoTrainer)."""
+        frozen = self._frozen_names()                   # requires_grad=False: no gradient, no update, no step counted (DESIGN.md §4.11)
+        self._check_freeze(frozen)
+        plain = self._plain_step(frozen)                # every tensor trains under the global step count: today's launches
         self._defer_tick, self._pending_drop_tick = True, 0
         n0 = visual.shape[0]
         loss = torch.empty(1, dtype=F32, device=self._device)
@@ -1254,14 +1398,15 @@ class AVM(nn.Module):
         # One GPU, no gradient exchange, no overflow guard to consult: linear5.weight (99.8 % of the parameters at 224 x 224) gets
         # its Adam pass the moment its gradient exists and its last reader of the step (the data gradient) is enqueued — on the
         # side stream, i.e. 36 GB of HBM traffic under the MFMA-bound convolution gradients that follow instead of after them
-        early = sync is None and self.precision != "fp16" and self._large_overlap(n) and self._fork_ok(n)
+        # (with frozen or re-thawed tensors the update is ONE launch over the trainable ranges after backward: no early pass)
+        early = plain and sync is None and self.precision != "fp16" and self._large_overlap(n) and self._fork_ok(n)
         # Small steps (the reference's 10-frame sub-batches): the same idea as a BACKGROUND pass — the update of linear5.weight (90 % of
         # the step's 0.66 GB of optimizer traffic) on a third stream and on a bounded number of blocks. Built, bit-identical, and
         # measured WITHOUT gain at any width (GOALNET_EARLY_ADAM_BLOCKS=64 / 128 / 256 / 512: 1 226 / 1 042 / 990 / 980 us per step
         # against 836 us without): every kernel of the backward chain is a few dependent memory round trips, and each of them
         # gets slower beside a stream that keeps the memory system busy. Off by default (0).
         bg_blocks = int(os.environ.get("GOALNET_EARLY_ADAM_BLOCKS", "0"))      # measured: 836 us without, 980-1230 us with 64-512 blocks
-        early_bg = (not early and sync is None and self.precision == "fp32" and self._w5b is None and n <= self.overlap_rows
+        early_bg = (plain and not early and sync is None and self.precision == "fp32" and self._w5b is None and n <= self.overlap_rows
                     and self._fork_ok(n) and bg_blocks > 0)
         done_early = []
 
@@ -1280,7 +1425,7 @@ class AVM(nn.Module):
                 fork.run(lambda: self._adam_range(s5.offset, s5.offset + s5.numel, lr, betas, eps, 1.0 / lscale))
             done_early.append((s5.offset, s5.offset + s5.numel))
         self.backward_device(ctx, dout, on_bucket=(lambda k: sync.on_bucket(self, k)) if sync is not None else None,
-                             after_linear5=early_adam if (early or early_bg) else None)
+                             after_linear5=early_adam if (early or early_bg) else None, frozen=frozen)
         scale = 1.0
         if sync is not None:
             scale = sync.finish(self)
@@ -1289,8 +1434,19 @@ class AVM(nn.Module):
             # an overflow anywhere in the 16-bit chain reaches the gradients computed last (conv1 ... bnorm3) and first (the
             # fusion MLP sees nothing 16-bit): checking the two small buckets (after the exchange: all ranks agree) is enough
             s5 = self.spec("visbl.linear5.weight")
-            after = min(s.offset for s in self._specs if s.offset > s5.offset)
-            ops.grad_finite_check(self._garena[after:], self._state[0], self._guard[0], self._guard[1])
+            if not frozen:
+                after = min(s.offset for s in self._specs if s.offset > s5.offset)
+                ops.grad_finite_check(self._garena[after:], self._state[0], self._guard[0], self._guard[1])
+            else:
+                # A pruned backward writes only the trainable slots: read those alone, never a frozen slot or slot padding. Every
+                # trainable tensor is checked except linear5.weight (the big one): an overflow of the forward reaches all of them
+                # through dL/dpred, one of the 16-bit backward chain reaches what is computed beneath it. Where nothing trains beneath
+                # linear5.weight, its own gradient is the only reader of the 16-bit dz5 and is checked too.
+                names = [s.name for s in self._specs if s.name not in frozen]
+                if any(k.startswith(("visbl.bnorm", "visbl.conv")) for k in names):
+                    names = [k for k in names if k != s5.name]
+                for lo, hi in self._exact_runs(names):
+                    ops.grad_finite_check(self._garena[lo:hi], self._state[0], self._guard[0], self._guard[1])
             guard = self._guard[0]
         self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early)
         if early_bg and done_early:
@@ -1370,8 +1526,32 @@ class AVM(nn.Module):
         counter state[0] (= completed steps) + 1, so the same captured launch serves every step. With a sharded
         linear5.weight (ddp.py) the pass covers this rank's slice only — three launches — and the optimizer state exists
         only for what the rank owns."""
+        frozen = self._bwd_frozen
+        self._check_freeze(frozen)
+        if self.precision == "fp16":
+            # a guard-skipped step is not counted on the device, so the host cannot keep the counts of sat-out steps without a read-back
+            if self._fp16_frozen is None:
+                self._fp16_frozen = frozen
+            elif self._fp16_frozen != frozen:
+                raise GoalnetError("precision='fp16': the set of frozen tensors may not change after the first optimizer step")
         segs = self._adam_state()
         self._adam_t += 1
+        if not self._plain_step(frozen):
+            # frozen tensors (or tensors that sat steps out and train again): ONE launch over the trainable ranges, each under its own
+            # step count; the optimizer state keeps the arena's layout, so nothing moves when a tensor is unfrozen
+            assert segs == [(0, self._arena_numel)] and not _done
+            ranges = trainable_ranges(self._specs, frozen, self._sat_out)
+            if len(ranges) > ops.ADAM_RANGES_MAX:
+                raise GoalnetError(f"{len(ranges)} trainable ranges: the fused Adam takes {ops.ADAM_RANGES_MAX}")
+            s5 = self.spec("visbl.linear5.weight")
+            shadow = self._w5b if (s5.name not in frozen and self._w5b is not None and self._w5b_version == self._w5_version()) else None
+            if ranges:
+                ops.adam_step_dev_ranges(self._arena, self._garena, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps,
+                                         self._state[0], grad_scale, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
+            self._count_sat_out(frozen)
+            if _tick:
+                ops.counter_add(self._state[0], 1)
+            return
         if _done:
             # ranges train_step already updated under backward (the early Adam on linear5.weight): the rest of the arena now
             assert segs == [(0, self._arena_numel)] and _guard is None
@@ -1418,9 +1598,12 @@ class AVM(nn.Module):
         s = scores.detach().to(device=self._device, dtype=F32).contiguous()
         return ops.argmax_plus1(s, torch.empty(s.shape[0], dtype=F32, device=self._device))
 
-    def grad_of(self, name) -> torch.Tensor:
-        """Gradient of a parameter as a strided view with the reference's logical shape (linear5: (512, C*HW) copy)."""
+    def grad_of(self, name) -> Optional[torch.Tensor]:
+        """Gradient of a parameter as a strided view with the reference's logical shape (linear5: (512, C*HW) copy); None for a
+        tensor that was frozen (requires_grad=False) in the last backward."""
         s = self.spec(name)
+        if name in self._bwd_frozen:
+            return None                       # frozen in the last backward: no gradient was produced
         v = self._view(self._garena, s)
         v = v.reshape(s.shape[0], -1) if s.kind == "lin5" else v
         # fp16: train_step leaves loss_scale x gradient in the arena (the fused Adam divides it out); the drop-in path unscales
@@ -1457,7 +1640,9 @@ class _AVMFunction(torch.autograd.Function):
         if lscale != 1.0:                                 # fp16: scaled through the 16-bit chain, unscaled before torch sees .grad
             dout = ops.scale_(dout.clone(), lscale)
         need = (ctx.needs_input_grad[4], ctx.needs_input_grad[5])
-        din = model.backward_device(saved, dout, inputs=need if any(need) else None)
+        # a parameter with requires_grad=False gets no gradient: autograd says which (needs_input_grad), and backward returns None for it
+        frozen = frozenset(s.name for s, k in zip(model._specs, ctx.needs_input_grad[6:]) if not k)
+        din = model.backward_device(saved, dout, inputs=need if any(need) else None, frozen=frozen)
         if lscale != 1.0:
             ops.scale_(model._garena, 1.0 / lscale)
             for d in din:
@@ -1465,7 +1650,7 @@ class _AVMFunction(torch.autograd.Function):
                     ops.scale_(d.view(-1), 1.0 / lscale)
         model._arena_grad_scale = 1.0
         ctx.saved = None
-        grads = [model._view(model._garena, s) for s in model._specs]
+        grads = [None if s.name in frozen else model._view(model._garena, s) for s in model._specs]
         # the inputs' gradients in the inputs' own shape, type and device (CPU leaves: one D2H copy)
         din = [None if (d is None or not k) else d.view(like.shape).to(device=like.device, dtype=like.dtype)
                for d, k, like in zip(din, need, ctx.inputs_like)]

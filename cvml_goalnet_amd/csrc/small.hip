@@ -401,6 +401,18 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
     p = p - step_size * (m / denom);           // param.addcdiv_(exp_avg, denom, value = -step_size)
 }
 
+// four updated parameters as binary16 (f16 != 0) or bfloat16, packed for one 8-byte store into the 16-bit copy
+__device__ __forceinline__ uint2 pack4_16(const float4& pp, int f16) {
+    if (f16) {
+        const _Float16 a = (_Float16)pp.x, b = (_Float16)pp.y, c = (_Float16)pp.z, d = (_Float16)pp.w;
+        return make_uint2((unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16),
+                          (unsigned)__builtin_bit_cast(unsigned short, c) | ((unsigned)__builtin_bit_cast(unsigned short, d) << 16));
+    }
+    const __hip_bfloat16 a = __float2bfloat16(pp.x), b = __float2bfloat16(pp.y), c = __float2bfloat16(pp.z), d = __float2bfloat16(pp.w);
+    return make_uint2((unsigned)*reinterpret_cast<const unsigned short*>(&a) | ((unsigned)*reinterpret_cast<const unsigned short*>(&b) << 16),
+                      (unsigned)*reinterpret_cast<const unsigned short*>(&c) | ((unsigned)*reinterpret_cast<const unsigned short*>(&d) << 16));
+}
+
 // One kernel for both entry points (host step count / device step counter) so that they produce the same bits.
 // The scalars torch's _single_tensor_adam computes as python floats (doubles) are computed in fp64 here.
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -429,19 +441,57 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
         if (shadow && i >= sh_b4 && i < sh_e4) {       // 16-bit copy of the updated parameters of one slice (the next step's GEMM operand)
-            if (sh_f16) {
-                const _Float16 a = (_Float16)pp.x, b = (_Float16)pp.y, c = (_Float16)pp.z, d = (_Float16)pp.w;
-                shadow[i - sh_b4] = make_uint2((unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16),
-                                               (unsigned)__builtin_bit_cast(unsigned short, c) | ((unsigned)__builtin_bit_cast(unsigned short, d) << 16));
-            } else {
-                const __hip_bfloat16 a = __float2bfloat16(pp.x), b = __float2bfloat16(pp.y), c = __float2bfloat16(pp.z), d = __float2bfloat16(pp.w);
-                shadow[i - sh_b4] = make_uint2((unsigned)*reinterpret_cast<const unsigned short*>(&a) | ((unsigned)*reinterpret_cast<const unsigned short*>(&b) << 16),
-                                               (unsigned)*reinterpret_cast<const unsigned short*>(&c) | ((unsigned)*reinterpret_cast<const unsigned short*>(&d) << 16));
-            }
+            shadow[i - sh_b4] = pack4_16(pp, sh_f16);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = (n4 << 2) + threadIdx.x;
+        adam1(p[i], g[i], m[i], v[i], b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
+    }
+}
+
+// The same update over up to GOALNET_ADAM_RANGES_MAX ranges of the arena in ONE launch (frozen tensors split the arena; a launch per
+// range would cost more than a small step saves). The descriptors travel by value in the kernel arguments, so a captured graph bakes
+// them. Blocks [first_block[r], first_block[r + 1]) serve range r and stride over it alone: no block spans two ranges. Range r runs
+// under its own step count *step + 1 - skipped[r] (torch.optim.Adam counts steps per parameter and skips those without a gradient);
+// element for element the arithmetic is adam_kernel's, so the result equals that kernel run range by range.
+struct AdamRanges {
+    int64_t begin[GOALNET_ADAM_RANGES_MAX], count[GOALNET_ADAM_RANGES_MAX], skipped[GOALNET_ADAM_RANGES_MAX];
+    int first_block[GOALNET_ADAM_RANGES_MAX + 1];
+};
+
+__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, AdamRanges rs, int nranges, double lr, double beta1,
+                                                         double beta2, float eps, const int64_t* __restrict__ step_dev, float gs,
+                                                         uint2* __restrict__ shadow, int64_t sh_b4, int64_t sh_e4, int sh_f16,
+                                                         const int64_t* __restrict__ bad_step) {
+    const int64_t t1 = *step_dev + 1;                     // the step's own count: what goalnet_grad_finite_check stamps
+    if (bad_step && *bad_step == t1) return;
+    int r = 0;
+    while (r + 1 < nranges && (int)blockIdx.x >= rs.first_block[r + 1]) ++r;
+    const int64_t lb = (int)blockIdx.x - rs.first_block[r], nb = rs.first_block[r + 1] - rs.first_block[r];
+    const double t = (double)(t1 - rs.skipped[r]);
+    const float step_size = (float)(lr / (1.0 - pow(beta1, t)));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
+    const float b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+    const int64_t begin = rs.begin[r], n = rs.count[r], b4 = begin >> 2, n4 = n >> 2;
+    for (int64_t j = lb * blockDim.x + threadIdx.x; j < n4; j += nb * blockDim.x) {
+        const int64_t i = b4 + j;                         // float4 index in the arena
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i];
+        float4 vv = reinterpret_cast<float4*>(v)[i];
+        adam1(pp.x, gg.x, mm.x, vv.x, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
+        adam1(pp.y, gg.y, mm.y, vv.y, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
+        adam1(pp.z, gg.z, mm.z, vv.z, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
+        adam1(pp.w, gg.w, mm.w, vv.w, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        if (shadow && i >= sh_b4 && i < sh_e4) shadow[i - sh_b4] = pack4_16(pp, sh_f16);
+    }
+    if (lb == 0 && threadIdx.x < (n & 3)) {
+        const int64_t i = begin + (n4 << 2) + threadIdx.x;
         adam1(p[i], g[i], m[i], v[i], b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
     }
 }
@@ -654,6 +704,38 @@ int goalnet_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, 
     }
     return adam_launch("adam_step_dev_guarded", p, g, m, v, n, lr, beta1, beta2, eps, step, step_bias, grad_scale, stream, shadow_16,
                        shadow_begin, shadow_16 ? shadow_count : 0, f16, bad_step);
+}
+
+/* goalnet_adam_step_dev[_guarded] over a list of arena ranges in one launch; range r runs under the count *step + 1 - skipped[r] */
+int goalnet_adam_step_dev_ranges(float* p, const float* g, float* m, float* v, const goalnet_adam_range* ranges, int count, double lr,
+                                 double beta1, double beta2, double eps, const int64_t* step, float grad_scale, void* shadow_16,
+                                 int64_t shadow_begin, int64_t shadow_count, int f16, const int64_t* bad_step, void* stream) {
+    GN_REQUIRE(p && g && m && v && ranges && step, GOALNET_E_NULL, "adam_step_dev_ranges: null pointer");
+    GN_REQUIRE(count >= 1 && count <= GOALNET_ADAM_RANGES_MAX, GOALNET_E_SHAPE, "adam_step_dev_ranges: 1..%d ranges", GOALNET_ADAM_RANGES_MAX);
+    GN_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), GOALNET_E_ALIGN, "adam_step_dev_ranges: arenas must be 16-byte aligned");
+    AdamRanges rs;
+    int64_t end = 0;
+    rs.first_block[0] = 0;
+    for (int r = 0; r < count; ++r) {
+        const goalnet_adam_range& a = ranges[r];
+        GN_REQUIRE(a.begin >= 0 && a.count > 0, GOALNET_E_SHAPE, "adam_step_dev_ranges: range %d is empty or starts below 0", r);
+        GN_REQUIRE(a.skipped >= 0, GOALNET_E_SHAPE, "adam_step_dev_ranges: range %d: negative count of skipped steps", r);
+        GN_REQUIRE((a.begin & 3) == 0, GOALNET_E_ALIGN, "adam_step_dev_ranges: range %d must begin at a multiple of 4 elements", r);
+        GN_REQUIRE(a.begin >= end, GOALNET_E_SHAPE, "adam_step_dev_ranges: range %d overlaps its predecessor or is out of order", r);
+        end = a.begin + a.count;
+        rs.begin[r] = a.begin; rs.count[r] = a.count; rs.skipped[r] = a.skipped;
+        rs.first_block[r + 1] = rs.first_block[r] + (int)grid1d(a.count >> 2, 8192);
+    }
+    if (shadow_16) {
+        GN_REQUIRE(shadow_begin >= 0 && shadow_count > 0 && (shadow_begin & 3) == 0 && (shadow_count & 3) == 0, GOALNET_E_SHAPE,
+                   "adam_step_dev_ranges: the shadowed slice's offset and length must be multiples of 4");
+        GN_REQUIRE((reinterpret_cast<uintptr_t>(shadow_16) & 7u) == 0, GOALNET_E_ALIGN, "adam_step_dev_ranges: shadow must be 8-byte aligned");
+    }
+    hipLaunchKernelGGL(adam_ranges_kernel, dim3((unsigned)rs.first_block[count]), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rs, count, lr,
+                       beta1, beta2, (float)eps, step, grad_scale, (uint2*)shadow_16, shadow_begin >> 2,
+                       shadow_16 ? (shadow_begin + shadow_count) >> 2 : 0, f16, bad_step);
+    GN_LAUNCH_CHECK("adam_step_dev_ranges");
+    return 0;
 }
 
 int goalnet_scale(float* x, int64_t n, float s, void* stream) {

@@ -42,7 +42,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -102,6 +102,7 @@ class VideoTrainer:
         """What an eager train_step does on the host besides launching kernels."""
         m = self.model
         m._adam_t += 1
+        m._count_sat_out(m._bwd_frozen)             # the replayed optimizer step: one more that the frozen tensors sat out
         if not m.training:
             return                                  # eval(): no dropout draw, BatchNorm buffers untouched
         if m.dropout_mode == "device":
@@ -117,7 +118,10 @@ class VideoTrainer:
             return
         # the loss scale is a host scalar baked into the captured launches; the mode picks other kernels (eval(): running-stat
         # BatchNorm, no dropout), so a graph captured in one mode is never replayed in the other
-        gkey = (n, m._loss_scale_for(n), m.training)
+        # Freezing (requires_grad=False) prunes the backward and bakes the fused Adam's ranges with their step counts into the launch:
+        # the key carries them (() while everything trains), so a changed trainable set is captured afresh and never replays a stale
+        # graph. While the set is stable the counts of its ranges are too — only frozen tensors sit steps out — and replays stay valid.
+        gkey = (n, m._loss_scale_for(n), m.trainable_signature(), m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -141,6 +145,7 @@ class VideoTrainer:
                 return
             saved = (m._adam_t, m._drop_step, [int(getattr(m.visbl, f"bnorm{i}").num_batches_tracked) for i in (1, 2, 3)],
                      m.keep_ctx)
+            sat_out = dict(m._sat_out)
             m.keep_ctx = False
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
@@ -150,6 +155,7 @@ class VideoTrainer:
                 self._pool = g.pool()
             # capturing launched nothing: undo the host-side counters the captured code advanced
             m._adam_t, m._drop_step, nbt, m.keep_ctx = saved
+            m._sat_out = sat_out
             for i, v in zip((1, 2, 3), nbt):
                 getattr(m.visbl, f"bnorm{i}").num_batches_tracked.fill_(v)
             self._graphs[gkey] = g

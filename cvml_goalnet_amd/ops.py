@@ -366,6 +366,7 @@ def conv3x3_wgrad(x, scale, shift, dy, dw, N, H, W, Cin, Cout):
 BF16 = torch.bfloat16
 F16 = torch.float16
 H16 = (BF16, F16)          # the 16-bit storage formats of the reduced-precision engine; the C ABI's `f16` flag = (dtype == float16)
+ADAM_RANGES_MAX = _lib.ADAM_RANGES_MAX     # ranges one adam_step_dev_ranges launch takes
 
 
 def _f16(*ts):
@@ -905,6 +906,23 @@ def adam_step_dev_guarded(p, g, m, v, lr, beta1, beta2, eps, step, bad_step, sha
     check(lib().goalnet_adam_step_dev_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, beta1, beta2, eps, _ctr(step),
                                               int(step_bias), grad_scale, _p(shadow), int(shadow_begin), 0 if shadow is None else shadow.numel(),
                                               0 if shadow is None else _f16(shadow), _ctr(bad_step), _s()), "adam_step_dev_guarded")
+
+
+def adam_step_dev_ranges(p, g, m, v, ranges, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=None, shadow_begin=0, bad_step=None):
+    """adam_step_dev[_guarded] over `ranges` = [(begin, count, skipped)] of the arenas p, g, m, v in ONE launch; a range's 1-based step
+    count is *step + 1 - skipped. `shadow` (16-bit) receives the updated arena[shadow_begin : shadow_begin + shadow.numel()]."""
+    _chk(p, g, m, v, shadow)
+    n = p.numel()
+    _req(g.numel() == n and m.numel() == n and v.numel() == n, "adam_step_dev_ranges: p, g, m, v must have the same size")
+    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"adam_step_dev_ranges: 1..{_lib.ADAM_RANGES_MAX} ranges")
+    _req(all(b >= 0 and c > 0 and b + c <= n for b, c, _ in ranges), "adam_step_dev_ranges: a range leaves the arena")
+    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
+         "adam_step_dev_ranges: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
+    arr = (_lib.AdamRange * len(ranges))(*[_lib.AdamRange(int(b), int(c), int(k)) for b, c, k in ranges])
+    check(lib().goalnet_adam_step_dev_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), arr, len(ranges), lr, beta1, beta2, eps,
+                                             _ctr(step), grad_scale, _p(shadow), int(shadow_begin), 0 if shadow is None else shadow.numel(),
+                                             0 if shadow is None else _f16(shadow), 0 if bad_step is None else _ctr(bad_step), _s()),
+          "adam_step_dev_ranges")
 
 
 def scale_(x, s):

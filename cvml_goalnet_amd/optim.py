@@ -7,7 +7,8 @@ parameter arena instead of torch's per-tensor passes over 30 strided views.
 Same defaults and the same arithmetic as torch's single-tensor Adam (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad,
 bias-corrected; `goalnet_adam_step_dev`, csrc/small.hip). The parameters must be those of ONE `AVM` (they are views of its arena, and
 autograd leaves their gradients in its gradient arena: `_AVMFunction.backward`); like the stock optimizer it may be constructed before
-the first forward (Lazy parameters). `zero_grad()` only drops the `.grad` references: the gradient arena is overwritten by every
+the first forward (Lazy parameters). Parameters with `requires_grad=False` are left alone, moments and step count included (pass all
+parameters or only the trainable ones). `zero_grad()` only drops the `.grad` references: the gradient arena is overwritten by every
 backward. State (`exp_avg`, `exp_avg_sq`, step) lives in the model (`AVM._adam_m`, `_adam_v`, the device step counter).
 """
 from __future__ import annotations
@@ -43,9 +44,13 @@ class Adam(torch.optim.Optimizer):
         if len(self.param_groups) != 1:
             raise RuntimeError("one parameter group: the arena is updated in one pass")
         g = self.param_groups[0]
-        want = {id(getattr(*m._module_of(s.name))) for s in m._specs}
-        if {id(p) for p in g["params"]} != want:
-            raise RuntimeError("cvml_goalnet_amd.optim.Adam steps ALL parameters of its AVM (model.parameters())")
+        # as torch.optim.Adam skips a parameter whose grad is None, the pass skips the tensors that were frozen (requires_grad=False)
+        # in the last backward: the optimizer holds either all parameters or exactly the trainable ones
+        every = {id(getattr(*m._module_of(s.name))) for s in m._specs}
+        trainable = {id(getattr(*m._module_of(s.name))) for s in m._specs if s.name not in m._bwd_frozen}
+        if {id(p) for p in g["params"]} not in (every, trainable):
+            raise RuntimeError("cvml_goalnet_amd.optim.Adam steps ALL parameters of its AVM (model.parameters()), or all that have "
+                               "requires_grad=True (filter(lambda p: p.requires_grad, model.parameters()))")
         m.adam_step(g["lr"], tuple(g["betas"]), g["eps"])
         return loss
 

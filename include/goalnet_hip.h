@@ -421,6 +421,18 @@ int goalnet_grad_finite_check(const float* g, int64_t n, const int64_t* step, in
 int goalnet_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                                   double eps, const int64_t* step, int64_t step_bias, float grad_scale, void* shadow_16 /* nullable */,
                                   int64_t shadow_begin, int64_t shadow_count, int f16, const int64_t* bad_step, void* stream);
+/* goalnet_adam_step_dev / _guarded over up to GOALNET_ADAM_RANGES_MAX ranges of the arena in ONE launch (fine-tuning: frozen tensors
+ * split the arena). p, g, m, v are the arena bases; `ranges` is a HOST array copied by value into the kernel arguments (a captured
+ * graph bakes it), sorted by begin, not overlapping, each begin a multiple of 4 elements. Range r runs under the 1-based step count
+ * *step + 1 - skipped (torch.optim.Adam counts steps per parameter and skips those without a gradient); its elements get bit for
+ * bit what goalnet_adam_step_dev gives for that slice with step_bias = 1 - skipped. shadow_begin / shadow_count (multiples of 4) are
+ * ARENA elements: the 16-bit copy is written where a range covers them. The guard compares *bad_step with *step + 1. */
+#define GOALNET_ADAM_RANGES_MAX 32
+typedef struct { int64_t begin, count, skipped; } goalnet_adam_range;   /* arena elements; t = *step + 1 - skipped */
+int goalnet_adam_step_dev_ranges(float* p, const float* g, float* m, float* v, const goalnet_adam_range* ranges, int count,
+                                 double lr, double beta1, double beta2, double eps, const int64_t* step, float grad_scale,
+                                 void* shadow_16 /* nullable */, int64_t shadow_begin, int64_t shadow_count, int f16,
+                                 const int64_t* bad_step /* nullable */, void* stream);
 /* goalnet_counters_add4 for a guarded step: when *bad_step == counters[0] + d0 (this step was stamped and its Adam skipped) the
  * step count does not advance — a skipped step is not counted, as with torch's GradScaler — and the stamp is cleared so that the
  * retry under the same count is judged on its own gradients; counters 1..3 advance as usual. */

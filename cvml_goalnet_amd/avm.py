@@ -127,6 +127,35 @@ class _Fork:
         self.keep.clear()
 
 
+class _Bwd:
+    """What ONE backward_device pass shares with _block_bwd / _conv_block_bwd: the side-stream fork, the trainable set (T, any_T) with
+    where each parameter gradient goes (G), and the bias-gradient partials of blocks 3 and 2 that go out together at the end of the pass."""
+
+    def __init__(self, model, train, fork):
+        self.model, self.train, self.fork = model, train, fork
+        self.scratch = {}              # name -> gradient of a tensor that is not trained, where a fused kernel cannot omit it
+        self.dbias = {}                # block -> (partials, channels)
+        self.T = train.__contains__
+
+    def any_T(self, *layers):
+        return any(f"{layer}.{leaf}" in self.train for layer in layers for leaf in ("weight", "bias"))
+
+    def G(self, name):
+        """the gradient arena's slot for a trained tensor; per-pass scratch for the small gradients a fused kernel cannot omit (BatchNorm
+        affine, the fused MLP, the heads, AudBl's Conv1d layers), never the arena. The GEMM-sized gradients have no scratch: every launch
+        that writes one is issued under T(name) alone."""
+        m = self.model
+        if name in self.train:
+            return m._gflat(name)
+        s = m.spec(name)
+        if s.kind in ("ohwi", "lin5") and name != "visbl.conv1.weight":      # conv1's comes from the launch that sums conv1.bias's
+            raise GoalnetError(f"a backward that does not train {name} asked for its gradient")
+        t = self.scratch.get(name)
+        if t is None:
+            t = self.scratch[name] = torch.empty(s.numel, dtype=F32, device=m._device)
+        return t
+
+
 class _Spec:
     __slots__ = ("name", "kind", "shape", "numel", "offset", "fan_in")
 
@@ -237,22 +266,26 @@ class AVM(_LazyFlags, nn.Module):
         self._w5b, self._w5b_version = None, None      # bf16 shadow of visbl.linear5.weight and the version stamps it matches
         self._load_count = 0                           # bumped by load_state_dict (its layout kernels write the arena directly)
         self._state = None             # int64[4] device counters: adam step, dropout draw, frame cursor, sub-batch index
-        self._defer_tick = False       # inside train_step: counters advance once, at the end (one launch)
-        self._pending_drop_tick = 0
         self._materialized = False
         self.grad_sync = None          # optional ddp.GradSync: gradient exchange between backward and Adam
         self.stat_sync = None          # optional ddp.SyncStats: BatchNorm sums and the loss over all ranks' frames
         self.grad_bf16 = os.environ.get("GOALNET_DZ16", "1") != "0"   # precision="bf16": bf16 BatchNorm-output gradients (backward_device)
         self.act_bf16 = os.environ.get("GOALNET_P16", "1") != "0"     # precision="bf16": pooled activations of blocks 2, 3 stored as bf16
+        # the A/B switches of DESIGN.md's table, read HERE and never again: a graph captured from a step bakes the routing in, so a
+        # value that could change between two steps of one model would apply to eager steps and not to replays
+        env = os.environ.get
+        self.x6_off = env("GOALNET_X6_OFF") == "1"                    # _x6_conv / _x6_linear5
+        self.x6_linear5 = env("GOALNET_X6_LINEAR5", "1") != "0"       # _x6_linear5
+        self.x3_wgrad2 = env("GOALNET_X3_WGRAD2", "1") != "0"         # fp16x3: conv2's weight gradient on split operands (forward_device)
+        self.x3_dgrad2 = env("GOALNET_X3_DGRAD2", "1") != "0"         # split precisions: conv2's data gradient on split operands (backward_device)
+        self.mlp_fused = env("GOALNET_MLP_FUSED", "1") != "0"         # _mlp_fused
+        self.small_bn = env("GOALNET_SMALL_BN", "1") != "0"           # _small_bn
+        self.force_bf5 = env("GOALNET_FORCE_BF5") == "1"              # _bf5
+        self.overlap_pair = env("GOALNET_OVERLAP_PAIR", "1") != "0"   # _pair
         self.keep_ctx = False          # tests: keep the last train_step's / input_gradients' saved tensors in last_ctx
         self.last_ctx = None
         self.last_used_w5b = False
         self._side_stream = None
-        self._adam_stream = None
-        self._dbias_pending = {}
-        self._scratch_grads = {}
-        self._fused_loss, self._fused_loss_done = None, False      # train_step -> forward_device: (labels, loss, dout) for the fused MLP launch
-        self._fork = _Fork(self, False)
         self.overlap_rows = int(os.environ.get("GOALNET_OVERLAP_ROWS", "64"))   # steps of <= this many frames fork their off-path work
         # Forking at LARGE sizes: off-path work (weight gradients, bias sums, AudBl) on the side stream AND the fused Adam over linear5.weight
         # there as soon as its gradient exists (train_step's "early Adam") — HBM-bound passes under MFMA-bound GEMMs and the other way
@@ -548,14 +581,16 @@ class AVM(_LazyFlags, nn.Module):
         self.dropout_mode = "given" if masks is not None else "off"
         self._given_masks = None if masks is None else [m.to(self._device, F32).contiguous() for m in masks]
 
-    def _masks(self, n: int):
+    def _masks(self, n: int, caller_ticks: bool = False):
+        """(the five masks, draws the CALLER still has to add to the device counter state[1]): with caller_ticks the draw is left for
+        the launch that advances all of train_step's counters at its end"""
         if not self.training or self.dropout_mode == "off":
-            return [None] * 5                    # eval(): the five dropouts are the identity and the draw counter stays put
+            return [None] * 5, 0                 # eval(): the five dropouts are the identity and the draw counter stays put
         if self.dropout_mode == "given":
             for m, wdt in zip(self._given_masks, (512, 512, 512, 256, 128)):
                 if tuple(m.shape) != (n, wdt):
                     raise RuntimeError(f"dropout mask shape {tuple(m.shape)} != {(n, wdt)}")
-            return list(self._given_masks)
+            return list(self._given_masks), 0
         # one launch for the five masks; the draw index is the device counter state[1] (graph-capturable)
         widths = (512, 512, 512, 256, 128)
         buf = torch.empty(n * sum(widths), dtype=F32, device=self._device)
@@ -563,12 +598,10 @@ class AVM(_LazyFlags, nn.Module):
         # concatenated batch; standard DDP: an independent stream per rank (ddp.GradSync.sync_params re-seeds)
         row0 = self.stat_sync.rank * n if self.stat_sync is not None else self.dropout_row_offset
         out = ops.dropout_masks_dev(buf, n, widths, self.dropout_seed, TID_DROP, 8, self._state[1], DROP_P, row_offset=row0)
-        if self._defer_tick:
-            self._pending_drop_tick = 1          # train_step advances all counters in one launch at its end
-        else:
+        if not caller_ticks:
             ops.counter_add(self._state[1], 1)
         self._drop_step += 1
-        return out
+        return out, int(caller_ticks)
 
     # ------------------------------------------------------------------------------------------
     # forward / backward on device tensors
@@ -654,7 +687,7 @@ class AVM(_LazyFlags, nn.Module):
     def _x6_conv(self, m, cout):
         """precision="bf16x6": does this convolution (m output pixels, cout output channels of the GEMM) run on split operands?
         Only where the 256 x 256 tile is filled; everything else runs the fp32-MFMA kernels."""
-        return self._x6 and m >= 65536 and cout >= 256 and os.environ.get("GOALNET_X6_OFF") != "1"
+        return self._x6 and m >= 65536 and cout >= 256 and not self.x6_off
 
     # split operands: every helper returns (parts tensor, magnitude word or None); `_osc(a, b)` = the epilogue scale of a GEMM of the two
     def _amax_of(self, x2d, rows, c, scale=None, shift=None, bnC=0):
@@ -680,17 +713,25 @@ class AVM(_LazyFlags, nn.Module):
 
     def _x6_linear5(self, n, k5):
         """precision="bf16x6": linear5's three contractions on split operands (>= 256 frames: the 256 x 256 tile)"""
-        return self._x6 and ops.linear_split_ok(self._parts, n, k5, 512) and os.environ.get("GOALNET_X6_OFF") != "1" and \
-            os.environ.get("GOALNET_X6_LINEAR5", "1") != "0"
+        return self._x6 and ops.linear_split_ok(self._parts, n, k5, 512) and not self.x6_off and self.x6_linear5
 
     def _mlp_fused(self, n):
         """the one-launch fusion MLP (csrc/mlp.hip): the regression head at the reference's sub-batch sizes"""
-        return n <= 16 and self.head == "regression" and os.environ.get("GOALNET_MLP_FUSED", "1") != "0"
+        return n <= 16 and self.head == "regression" and self.mlp_fused
+
+    def _bf5(self, n):
+        """16-bit modes: linear5 on the 16-bit MFMA kernels? At <= 16 rows it is a pure weight stream: the fp32 weight-streaming kernels
+        (csrc/skinny.hip) read the arena once, which is cheaper (and exact) compared with casting 4 K J bytes to bf16 first"""
+        return self._half and (n > 16 or self.force_bf5)
+
+    def _pair(self, n):
+        """a forked LARGE step: each weight gradient goes out behind its layer's data gradient (comment in backward_device)"""
+        return self._large_overlap(n) and self.overlap_pair
 
     def _small_bn(self, a, b, n, hc, wc, c):
         """the one-launch pool / BatchNorm kernels (csrc/pool_bn.hip, goalnet_*_fused): fp32 tensors, local statistics, few elements"""
         return (a.dtype == F32 and b.dtype == F32 and self.stat_sync is None and c <= 512 and n * hc * wc * c <= ops.SMALL_BN_ELEMS
-                and os.environ.get("GOALNET_SMALL_BN", "1") != "0")
+                and self.small_bn)
 
     def _bn_block(self, y, n, hc, wc, c, i, save, p16=False):
         """maxpool + BN statistics of block i on conv output y (N,hc,wc,c). Returns (p, idx, mean, invstd, scale, shift).
@@ -759,8 +800,10 @@ class AVM(_LazyFlags, nn.Module):
         # the conv output is only an input of the pool: backward reads the ReLU mask off p (csrc/pool_bn.hip)
         return (*self._bn_block(y, n, hc, wc, cout, i, save, p16=p16), xh)
 
-    def forward_device(self, audio, visual, save: bool):
-        """audio (N,30,B) / None, visual (N,3,H,W): contiguous fp32 GPU tensors. Returns out (N,) [, ctx]."""
+    def forward_device(self, audio, visual, save: bool, *, fused_loss=None, caller_ticks: bool = False):
+        """audio (N,30,B) / None, visual (N,3,H,W): contiguous fp32 GPU tensors. Returns (out (N,), ctx); ctx is None unless `save`.
+        train_step's two riders: `fused_loss` = (labels, loss, dout) — where the one-launch MLP runs, it evaluates the broadcast MSE too
+        (ctx["loss_done"] says whether it did); `caller_ticks`: the dropout draw counter is advanced by the caller, by ctx["drop_ticks"]."""
         if visual.dim() != 4 or visual.shape[1] != 3:
             raise RuntimeError(f"visual_input must be (N,3,H,W), got {tuple(visual.shape)}")
         n, _, h, w = visual.shape
@@ -779,8 +822,9 @@ class AVM(_LazyFlags, nn.Module):
             self.grad_sync.ensure_params_synced(self)      # first synchronised step: every rank starts from rank 0's model
         dev = self._device
         P = self._pflat
-        masks = self._masks(n)
-        ctx = {"n": n, "h": h, "w": w, "bins": bins, "visual": visual, "audio": audio, "eval": not self.training} if save else None
+        masks, drop_ticks = self._masks(n, caller_ticks)
+        ctx = {"n": n, "h": h, "w": w, "bins": bins, "visual": visual, "audio": audio, "eval": not self.training,
+               "drop_ticks": drop_ticks, "loss_done": False} if save else None
 
         fw = 640 if self.audio_included else 512
         voff = fw - 512
@@ -814,10 +858,8 @@ class AVM(_LazyFlags, nn.Module):
         # segments — no gain; with three (fp16x3) 6.5 + 3.3 against 14-20: taken. conv3 keeps its split operands in both modes.
         p2, idx2, st2, xh1 = self._conv_block_fwd(
             2, p1, st1, n, *b2, save, ctx, p16=bf and self.act_bf16 and self._p16_ok(wp1, 256),
-            keep_split=self._parts == 2 and os.environ.get("GOALNET_X3_WGRAD2", "1") != "0")
-        # <= 16 rows: linear5 is a pure weight stream; the fp32 weight-streaming kernels (csrc/skinny.hip) read the
-        # arena once, which is cheaper (and exact) compared with casting 4 K J bytes to bf16 first
-        bf5 = bf and (n > 16 or os.environ.get("GOALNET_FORCE_BF5") == "1")
+            keep_split=self._parts == 2 and self.x3_wgrad2)
+        bf5 = self._bf5(n)
         # p3 is linear5's operand: 16-bit only where linear5 runs its 16-bit kernels (bf5), i.e. fp32 for n <= 16
         p3, idx3, st3, xh2 = self._conv_block_fwd(
             3, p2, st2, n, *b3, save, ctx, p16=bf5 and self.act_bf16 and self._p16_ok(wp2, 512), keep_split=True)
@@ -864,10 +906,10 @@ class AVM(_LazyFlags, nn.Module):
                 ms.append(torch.empty(n, width, dtype=F32, device=dev) if save else None)
             logit = torch.empty(n, dtype=F32, device=dev)
             out = torch.empty(n, dtype=F32, device=dev)
-            fl = self._fused_loss                    # train_step: the broadcast MSE rides in the same launch
             ops.mlp_fwd(cat, [P(f"fusion.{k}.weight") for k in keys], [P(f"fusion.{k}.bias") for k in keys], masks[1:5],
-                        hs[1:], ms[1:], logit, out, *(fl if fl is not None else (None, None, None)))
-            self._fused_loss_done = fl is not None
+                        hs[1:], ms[1:], logit, out, *(fused_loss if fused_loss is not None else (None, None, None)))
+            if save:
+                ctx["loss_done"] = fused_loss is not None    # train_step: the broadcast MSE rode in the same launch
             x = hs[4]
         for li, (key, width) in enumerate(() if fused_mlp else (("0", 512), ("3", 512), ("6", 256), ("9", 128))):
             hnext = torch.empty(n, width, dtype=F32, device=dev)
@@ -891,35 +933,31 @@ class AVM(_LazyFlags, nn.Module):
         self.last_features = cat                    # the fusion input (N, 512 | 640): what TemporalSegmenter segments (no copy)
         return out, ctx
 
-    def _block_bwd(self, dbn, ctx, i, n, hc, wc, c, G=None, bias=True):
+    def _block_bwd(self, bwd, dbn, ctx, i, n, hc, wc, c):
         """BN backward + max-pool backward + ReLU backward of block i. dbn = grad wrt the BN output (N,hc-2,wc-2,c).
-        Returns dy (N,hc,wc,c) = grad wrt the conv's pre-ReLU output; writes dgamma, dbeta, dbias where G(name) says (the grad arena;
+        Returns dy (N,hc,wc,c) = grad wrt the conv's pre-ReLU output; writes dgamma, dbeta, dbias where bwd.G(name) says (the grad arena;
         scratch for a frozen tensor and in the inputs-only backward: the fused kernels cannot omit dgamma / dbeta).
-        bias=False: conv{i}.bias is not trained — no bias sums."""
-        dev = self._device
-        G = G or self._gflat
+        No bias sums where conv{i}.bias is not trained."""
+        dev, G, bias = self._device, bwd.G, bwd.T(f"visbl.conv{i}.bias")
         p, idx, st = ctx[f"p{i}"], ctx[f"idx{i}"], ctx[f"st{i}"]
         npix = n * (hc - 2) * (wc - 2)
         small = self._small_bn(dbn, p, n, hc, wc, c) and not (self._half and i > 1)
         frozen = ctx["eval"]          # the forward ran under eval(): st holds the running statistics, constants of the forward
         if small:
             # the reference's operating point: reduce + finalise in one launch (csrc/pool_bn.hip "small shapes"), then the rolling-row
-            # max-pool / ReLU backward (13 us; the one-launch 9-window gather from global memory 35), its bias-gradient rows summed at
-            # the end of backward on the side stream
+            # max-pool / ReLU backward (13 us; the one-launch 9-window gather from global memory, ops.bnpool_bwd_small, measured 35), its
+            # bias-gradient rows summed at the end of backward on the side stream
             coef3 = torch.empty(3 * c, dtype=F32, device=dev)
             (ops.bn_bwd_reduce_small_eval if frozen else ops.bn_bwd_reduce_small)(
                 dbn, p, st[0], st[1], self._pflat(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.weight"), G(f"visbl.bnorm{i}.bias"),
                 coef3, n, hc, wc, c)
             dy = torch.empty(n, hc, wc, c, dtype=F32, device=dev)
-            if os.environ.get("GOALNET_SMALL_BNPOOL", "0") == "1":
-                ops.bnpool_bwd_small(dbn, p, idx, coef3, dy, G(f"visbl.conv{i}.bias"), n, hc, wc, c)
-                return dy
             dparts = torch.empty(ops.stat_parts(8 * n) * c, dtype=torch.float64, device=dev)
             ops.bnpool_bwd(dbn, p, idx, coef3, dy, dparts, n, hc, wc, c)
             # the bias gradients' row sums feed nothing but Adam: conv3's and conv2's go out together at the end of backward (one
             # launch, side stream); conv1's is written by goalnet_conv1_wgrad from its own sums of dy
             if i > 1 and bias:
-                self._dbias_pending[i] = (dparts, c)
+                bwd.dbias[i] = (dparts, c)
             return dy
         coef3 = torch.empty(3 * c, dtype=F32, device=dev)
         partials = torch.empty(ops.stat_parts(npix // 64) * 2 * c, dtype=torch.float64, device=dev)
@@ -958,37 +996,33 @@ class AVM(_LazyFlags, nn.Module):
             # one on the main stream too so that the order of the two writers does not depend on the schedule
             ops.partials_sum(dparts, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias"))
         else:
-            self._fork.run(lambda: ops.partials_sum(dparts, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias")), dparts)
+            bwd.fork.run(lambda: ops.partials_sum(dparts, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias")), dparts)
         return dy
 
-    def _conv_block_bwd(self, i, dbn, ctx, n, hc, wc, cin, cout, wt, flipped, wait_ev, pair, out16, split_dgrad, after_block=None,
-                        G=None, train=(True, True), dgrad=True):
+    def _conv_block_bwd(self, bwd, i, dbn, ctx, n, hc, wc, cin, cout, wt, flipped, wait_ev, pair, out16, split_dgrad, after_block=None,
+                        dgrad=True):
         """Backward of block i (2 or 3): from dbn = grad wrt its BatchNorm output (N,hc-2,wc-2,cout) to the grad wrt block i-1's
         BatchNorm output (N,hc,wc,cin), returned. _block_bwd, then conv{i}'s weight gradient (side stream, into the arena) and data
         gradient on the engine its forward ran on (_conv_block_fwd).
         wt: buffer for the flipped weight (csrc/layout.hip); flipped: the joint early launch fills it, and wait_ev is that launch's
         event where this block is its first reader. pair: the weight gradient goes out behind the data gradient (backward_device).
         out16: the data gradient may be stored in 16 bits; split_dgrad: it runs on split operands where the forward saved them;
-        after_block(): called between _block_bwd and the weight gradient. train = (conv{i}.weight, conv{i}.bias) are trained: no
-        weight-gradient launch / no bias sums otherwise; dgrad=False: nothing beneath this block wants a gradient — no data gradient,
-        None is returned. G: where a parameter gradient goes (_block_bwd)."""
-        dev, P, G, fork = self._device, self._pflat, G or self._gflat, self._fork
+        after_block(): called between _block_bwd and the weight gradient. No weight-gradient launch where conv{i}.weight is not trained
+        (bwd.T); dgrad=False: nothing beneath this block wants a gradient — no data gradient, None is returned."""
+        dev, P, G, fork = self._device, self._pflat, bwd.G, bwd.fork
         wname, xs = f"visbl.conv{i}.weight", f"x{i - 1}s"
         flops = 2.0 * n * hc * wc * 9 * cin * cout           # the same for the weight gradient and the data gradient
-        dy = self._block_bwd(dbn, ctx, i, n, hc, wc, cout, G, train[1])
+        dy = self._block_bwd(bwd, dbn, ctx, i, n, hc, wc, cout)
         if after_block:
             after_block()
         split = not self._half and xs in ctx           # the forward ran this convolution on split operands and kept them
-        if not train[0]:
+        if not bwd.T(wname):
             wg = None
             if split and split_dgrad and dgrad:
                 dys, ady = self._split_act(f"dy{i}s", dy, None, None, n, hc, wc, cout)
         elif self._half:
             wg, keep = (ops.conv3x3_wgrad_bf16, ctx[f"xh{i - 1}"], dy, G(wname), n, hc, wc, cin, cout), (dy,)
         elif split:
-            if ctx[xs + "_gen"] != self._padgen[xs]:
-                raise RuntimeError(f"precision='{self.precision}': a second training-mode forward overwrote the saved split operands "
-                                   "before backward ran; call backward after each forward (as the reference's loop does)")
             # the weight gradient and the data gradient read the gradient as 16-bit parts in the padded layout: one split pass
             dys, ady = self._split_act(f"dy{i}s", dy, None, None, n, hc, wc, cout)
             osc_w = self._osc(ady, ctx[xs + "_amax"])
@@ -1027,50 +1061,46 @@ class AVM(_LazyFlags, nn.Module):
             wgrad()                                  # behind the data gradient: runs under the next block's BatchNorm / pool passes
         return dx
 
-    def _gscratch(self, name):
-        """inputs-only backward: where a fused kernel cannot omit a small parameter gradient (BatchNorm affine, the fused MLP, the
-        heads, AudBl's Conv1d layers) it writes here, never into the arena. The GEMM-sized gradients have no slot."""
-        s = self.spec(name)
-        if s.kind in ("ohwi", "lin5") and name != "visbl.conv1.weight":      # conv1's comes from the launch that sums conv1.bias's
-            raise GoalnetError(f"a backward that does not train {name} asked for its gradient")
-        t = self._scratch_grads.get(name)
-        if t is None:
-            t = self._scratch_grads[name] = torch.empty(s.numel, dtype=F32, device=self._device)
-        return t
-
     def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None, inputs=None, params=True, reduce=0, frozen=None):
         """dout (N,) GPU. Fills the gradient arena (the slot of every TRAINABLE tensor is overwritten). `inputs` = (audio?, visual?): also
         follow the data-gradient chain into the inputs and return (d_audio (N,30,B) | None, d_visual (N,3,H,W) | None) — `reduce`=1:
         d_visual is max_ci |.|, (N,H,W).
         `frozen`: names of the tensors that are not trained (default: those whose nn.Parameter has requires_grad=False, read here, at
         the start of the backward). A frozen tensor gets no gradient: a launch whose only outputs are frozen gradients is not issued,
-        what a fused kernel cannot omit goes to _gscratch, and each branch of the data-gradient chain stops below its lowest trainable
+        what a fused kernel cannot omit goes to scratch (_Bwd.G), and each branch of the data-gradient chain stops below its lowest trainable
         tensor unless an input gradient is asked for. Gradients of trainable tensors are the same bits either way.
         params=False: the inputs-only backward — every tensor counts as frozen, and neither the arena nor any .grad is touched.
         `on_bucket(k)` is called when
         bucket k of ddp.bucket_slices() is complete (0: fusion+audbl+linear5.bias, 1: linear5.weight, 2: rest).
         `after_linear5(fork)`: called once linear5's weight gradient (side stream) and data gradient (main stream) are both
-        enqueued — from there on nothing reads linear5.weight or its 16-bit copy again in this step (train_step's early Adam)."""
+        enqueued — from there on nothing reads linear5.weight or its 16-bit copy again in this step (train_step's early Adam).
+        Every refusal is raised before the first launch or allocation, as on the C side: a refused call leaves the gradient arena and
+        both streams as they were."""
         need_aud, need_vis = inputs if inputs is not None else (False, False)
         need_aud = need_aud and self.audio_included
-        self._scratch_grads = {}
+        train = frozenset()
         if params:
-            self._ensure_garena()
             frozen = self._frozen_names() if frozen is None else frozenset(frozen)
             self._check_freeze(frozen)
-            self._bwd_frozen = frozen
             train = frozenset(s.name for s in self._specs) - frozen
-        else:
-            train = frozenset()
-        T = train.__contains__
-
-        def G(name):
-            return self._gflat(name) if name in train else self._gscratch(name)
-
-        def any_T(*layers):
-            return any(f"{layer}.{leaf}" in train for layer in layers for leaf in ("weight", "bias"))
+        # the operands the forward left in the cached padded buffers must still be the ones this ctx saved
+        if self._half and ctx["padgen"] != (self._padgen["x1"], self._padgen["x2"]):
+            raise RuntimeError("precision='bf16': a second training-mode forward overwrote the saved bf16 operands before "
+                               "backward ran; call backward after each forward (as the reference's loop does)")
+        for i in (3, 2):
+            # split operands: the weight gradient of conv{i} is their only reader in backward, and a trained weight means the block runs
+            xs = f"x{i - 1}s"
+            if not self._half and xs in ctx and f"visbl.conv{i}.weight" in train and ctx[xs + "_gen"] != self._padgen[xs]:
+                raise RuntimeError(f"precision='{self.precision}': a second training-mode forward overwrote the saved split operands "
+                                   "before backward ran; call backward after each forward (as the reference's loop does)")
+        if params:
+            self._ensure_garena()
+            self._bwd_frozen = frozen
         dev = self._device
         n, h, w = ctx["n"], ctx["h"], ctx["w"]
+        # small steps: weight / bias gradients and the AudBl branch run on a side stream under the dX chain (_Fork)
+        bwd = _Bwd(self, train, _Fork(self, self._fork_ok(n) and dout.is_cuda))
+        fork, T, G, any_T = bwd.fork, bwd.T, bwd.G, bwd.any_T
         (h1, w1), (hp1, wp1), (hp2, wp2), (hp3, wp3) = self._sizes(h, w)
         P = self._pflat
         # what each stage of the VisBl chain is needed for: block i's BatchNorm / pool / ReLU backward (b_i) feeds its own parameters and
@@ -1084,16 +1114,13 @@ class AVM(_LazyFlags, nn.Module):
         d_audio = torch.empty(n, 30, ctx["bins"], dtype=F32, device=dev) if need_aud else None
         d_visual = None
         hs, ms = ctx["hs"], ctx["ms"]
-        # small steps: weight / bias gradients and the AudBl branch run on a side stream under the dX chain (_Fork)
-        fork = self._fork = _Fork(self, self._fork_ok(n) and dout.is_cuda)
-        self._dbias_pending = {}
         # Large steps (forked by _large_overlap): the side stream's pieces are paired with main-stream work of the OTHER kind — linear5's
         # Adam (HBM-bound) goes out when conv3's data gradient (MFMA-bound) starts, each weight gradient (MFMA-bound) when its layer's
         # data gradient is enqueued, i.e. under the BatchNorm / pool passes of the next block (HBM-bound). Small steps keep the weight
         # gradient FIRST: there the chain is latency-bound and everything off it should start as early as it can. Same kernels, same
         # results either way. Measured (1 024 frames, alternating runs): fp16x3 178.5 -> 176.9 ms, bf16 70.6 -> 70.6 (GOALNET_OVERLAP_PAIR=0
         # restores the weight-gradient-first order).
-        pair = fork.enabled and self._large_overlap(n) and os.environ.get("GOALNET_OVERLAP_PAIR", "1") != "0"
+        pair = fork.enabled and self._pair(n)
         deferred_l5 = []
 
         def bucket_done(k):
@@ -1178,9 +1205,6 @@ class AVM(_LazyFlags, nn.Module):
         # stored as bf16 (fp32 accumulators rounded once, at the store): its only readers are the two HBM-bound passes of
         # _block_bwd, and the GEMMs behind them consume bf16 anyway
         dz16 = bf and self.grad_bf16
-        if bf and ctx["padgen"] != (self._padgen["x1"], self._padgen["x2"]):
-            raise RuntimeError("precision='bf16': a second training-mode forward overwrote the saved bf16 operands before "
-                               "backward ran; call backward after each forward (as the reference's loop does)")
         dbn3 = None
         if chain and (train_w5 or need_b3):
             p3f = ctx["p3"].view(n, k5)
@@ -1228,38 +1252,33 @@ class AVM(_LazyFlags, nn.Module):
             # block 3 (utils.py:184-187): the first reader of the flipped weights (waits for the joint early launch). Its data gradient
             # is kept in 16 bits where BLOCK 2's fused backward reads that (_bwd16_ok of block 2's width). pair: linear5's Adam starts
             # behind _block_bwd, beside conv3's data gradient
-            dbn2 = self._conv_block_bwd(3, dbn3, ctx, n, *b3, wt3, flips_early, flips_ev, pair, out16=dz16 and self._bwd16_ok(wp1),
-                                        split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5], G=G,
-                                        train=(T("visbl.conv3.weight"), T("visbl.conv3.bias")), dgrad=need_b2)
+            dbn2 = self._conv_block_bwd(bwd, 3, dbn3, ctx, n, *b3, wt3, flips_early, flips_ev, pair, out16=dz16 and self._bwd16_ok(wp1),
+                                        split_dgrad=True, after_block=lambda: [cb(fork) for cb in deferred_l5], dgrad=need_b2)
         del dbn3
         if dbn2 is not None:
             # block 2 (utils.py:179-182): no wait (conv3's covered the joint flip launch); dbn1 is always fp32, its consumer is block 1's
             # fp32 path; fp16x3: the split gradient is there already (weight gradient) -> 128 x 64 tile, three segments
-            dbn1 = self._conv_block_bwd(2, dbn2, ctx, n, *b2, wt2, flips_early, None, pair, out16=False,
-                                        split_dgrad=os.environ.get("GOALNET_X3_DGRAD2", "1") != "0", G=G,
-                                        train=(T("visbl.conv2.weight"), T("visbl.conv2.bias")), dgrad=need_b1)
+            dbn1 = self._conv_block_bwd(bwd, 2, dbn2, ctx, n, *b2, wt2, flips_early, None, pair, out16=False,
+                                        split_dgrad=self.x3_dgrad2, dgrad=need_b1)
         del dbn2
 
         if dbn1 is not None:
             # block 1 (utils.py:174-177); conv1's input gradient only where it was asked for (dy1 is fp32 in every precision)
             train_c1 = any_T("visbl.conv1")
-            dy1 = self._block_bwd(dbn1, ctx, 1, n, h1, w1, 64, G, T("visbl.conv1.bias"))
+            dy1 = self._block_bwd(bwd, dbn1, ctx, 1, n, h1, w1, 64)
             if train_c1:
                 ops.conv1_wgrad(ctx["visual"], dy1, G("visbl.conv1.weight"), G("visbl.conv1.bias"), n, h, w)
             if need_vis:
                 d_visual = ops.conv1_dgrad(dy1, P("visbl.conv1.weight"), torch.empty((n, h, w) if reduce else (n, 3, h, w), dtype=F32, device=dev),
                                            reduce, n, h, w)
-        if len(self._dbias_pending) == 2:
-            (d3, _), (d2, _) = self._dbias_pending[3], self._dbias_pending[2]
+        if len(bwd.dbias) == 2:
+            (d3, _), (d2, _) = bwd.dbias[3], bwd.dbias[2]
             fork.run(lambda: ops.partials_sum2(d3, 512, G("visbl.conv3.bias"), d2, 256, G("visbl.conv2.bias")), d3, d2)
         else:
             # one of the two blocks did not run or does not train its bias: the same column sums, one array
-            for i, (dp, c) in self._dbias_pending.items():
+            for i, (dp, c) in bwd.dbias.items():
                 fork.run(lambda i=i, dp=dp, c=c: ops.partials_sum(dp, ops.stat_parts(8 * n), c, c, G(f"visbl.conv{i}.bias")), dp)
-        self._dbias_pending = {}
         fork.join()                                 # every gradient is in the arena before anything downstream (Adam, all-reduce) reads it
-        self._fork = _Fork(self, False)
-        self._scratch_grads = {}
         if on_bucket:
             on_bucket(2)
         return d_audio, d_visual
@@ -1361,21 +1380,16 @@ class AVM(_LazyFlags, nn.Module):
         frozen = self._frozen_names()                   # requires_grad=False: no gradient, no update, no step counted
         self._check_freeze(frozen)
         plain = self._plain_step(frozen)                # every tensor trains under the global step count: today's launches
-        self._defer_tick, self._pending_drop_tick = True, 0
         n0 = visual.shape[0]
         loss = torch.empty(1, dtype=F32, device=self._device)
         dout = torch.empty(n0 if self.head == "regression" else (n0, self.num_classes), dtype=F32, device=self._device)
         # the regression head's broadcast MSE is evaluated by the fused MLP launch itself where that launch exists (<= 16 rows)
         lab32 = labels if (torch.is_tensor(labels) and labels.dtype == F32 and labels.is_contiguous() and labels.is_cuda) else None
-        self._fused_loss = (lab32, loss, dout) if (self.stat_sync is None and lab32 is not None and self._mlp_fused(n0)) else None
-        self._fused_loss_done = False
-        try:
-            out, ctx = self.forward_device(audio, visual, save=True)
-        finally:
-            self._defer_tick = False
-            self._fused_loss = None
+        fused_loss = (lab32, loss, dout) if (self.stat_sync is None and lab32 is not None and self._mlp_fused(n0)) else None
+        # the dropout draw counter advances with the step's other counters, in the one launch at the end
+        out, ctx = self.forward_device(audio, visual, save=True, fused_loss=fused_loss, caller_ticks=True)
         n = out.shape[0]
-        if self._fused_loss_done:
+        if ctx["loss_done"]:
             pass
         elif self.head == "classifier":
             if self.stat_sync is not None:
@@ -1400,32 +1414,20 @@ class AVM(_LazyFlags, nn.Module):
         # side stream, i.e. 36 GB of HBM traffic under the MFMA-bound convolution gradients that follow instead of after them
         # (with frozen or re-thawed tensors the update is ONE launch over the trainable ranges after backward: no early pass)
         early = plain and sync is None and self.precision != "fp16" and self._large_overlap(n) and self._fork_ok(n)
-        # Small steps (the reference's 10-frame sub-batches): the same idea as a BACKGROUND pass — the update of linear5.weight (90 % of
-        # the step's 0.66 GB of optimizer traffic) on a third stream and on a bounded number of blocks. Built, bit-identical, and
-        # measured WITHOUT gain at any width (GOALNET_EARLY_ADAM_BLOCKS=64 / 128 / 256 / 512: 1 226 / 1 042 / 990 / 980 us per step
-        # against 836 us without): every kernel of the backward chain is a few dependent memory round trips, and each of them
-        # gets slower beside a stream that keeps the memory system busy. Off by default (0).
-        bg_blocks = int(os.environ.get("GOALNET_EARLY_ADAM_BLOCKS", "0"))      # measured: 836 us without, 980-1230 us with 64-512 blocks
-        early_bg = (plain and not early and sync is None and self.precision == "fp32" and self._w5b is None and n <= self.overlap_rows
-                    and self._fork_ok(n) and bg_blocks > 0)
+        # (small steps: the same update as a background pass on a third stream was measured slower at every width)
         done_early = []
 
         def early_adam(fork):
             s5 = self.spec("visbl.linear5.weight")
-            if early_bg:
-                if self._adam_stream is None:
-                    self._adam_stream = torch.cuda.Stream(device=self._device)
-                st = self._adam_stream
-                st.wait_stream(torch.cuda.current_stream())       # the data gradient (last reader of the weights) is enqueued
-                if fork.enabled:
-                    st.wait_stream(fork.side)                      # the weight gradient runs on the side stream
-                with torch.cuda.stream(st):
-                    self._adam_range(s5.offset, s5.offset + s5.numel, lr, betas, eps, 1.0 / lscale, max_blocks=bg_blocks)
-            else:
-                fork.run(lambda: self._adam_range(s5.offset, s5.offset + s5.numel, lr, betas, eps, 1.0 / lscale))
-            done_early.append((s5.offset, s5.offset + s5.numel))
+            lo, hi = s5.offset, s5.offset + s5.numel
+
+            def piece():
+                self._adam_state()                   # the first step allocates the moments
+                self._adam_piece(lo, hi, lo, lr, betas, eps, 1.0 / lscale)
+            fork.run(piece)
+            done_early.append((lo, hi))
         self.backward_device(ctx, dout, on_bucket=(lambda k: sync.on_bucket(self, k)) if sync is not None else None,
-                             after_linear5=early_adam if (early or early_bg) else None, frozen=frozen)
+                             after_linear5=early_adam if early else None, frozen=frozen)
         scale = 1.0
         if sync is not None:
             scale = sync.finish(self)
@@ -1449,16 +1451,14 @@ class AVM(_LazyFlags, nn.Module):
                     ops.grad_finite_check(self._garena[lo:hi], self._state[0], self._guard[0], self._guard[1])
             guard = self._guard[0]
         self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early)
-        if early_bg and done_early:
-            torch.cuda.current_stream().wait_stream(self._adam_stream)     # the background pass joins before the step count moves
         if _scatter is not None:
-            ops.rows_scatter_tick(_scatter(loss, out), self._state, 1, self._pending_drop_tick, _loop_tick[0], _loop_tick[1], bad_step=guard)
+            ops.rows_scatter_tick(_scatter(loss, out), self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], bad_step=guard)
         elif guard is not None:
             # a step whose Adam was skipped is not counted (torch's GradScaler does not count it either): the retry runs under
             # the same step count; `_adam_t` on the host counts ATTEMPTED steps
-            ops.counters_add4_guarded(self._state, 1, self._pending_drop_tick, _loop_tick[0], _loop_tick[1], guard)
+            ops.counters_add4_guarded(self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], guard)
         else:
-            ops.counters_add4(self._state, 1, self._pending_drop_tick, _loop_tick[0], _loop_tick[1])
+            ops.counters_add4(self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1])
         return loss, out
 
     def _adam_segments(self):
@@ -1505,19 +1505,23 @@ class AVM(_LazyFlags, nn.Module):
             self._adam_segs = segs
         return segs
 
-    def _adam_range(self, lo, hi, lr, betas, eps, grad_scale, max_blocks=0):
-        """the fused Adam on arena[lo:hi] (unsharded optimizer state: moments live at the arena's offsets); refreshes the part of
-        the 16-bit copy of linear5.weight that lies inside. The step counter is NOT advanced (train_step does that once)."""
-        segs = self._adam_state()
-        assert segs == [(0, self._arena_numel)]
+    def _adam_piece(self, lo, hi, moff, lr, betas, eps, grad_scale, guard=None):
+        """the fused Adam on arena[lo:hi] against the moments at [moff, moff + hi - lo) (moff = lo unless the optimizer state is sharded).
+        Refreshes the part of the valid 16-bit copy of linear5.weight that lies inside, in the same pass (the kernels do not bump
+        versions). `guard` (fp16): the pass is skipped as a whole when this step's gradients overflowed (goalnet_grad_finite_check).
+        The step counter is NOT advanced."""
         s5 = self.spec("visbl.linear5.weight")
-        p, g, m, v = self._arena[lo:hi], self._garena[lo:hi], self._adam_m[lo:hi], self._adam_v[lo:hi]
-        a, b = max(lo, s5.offset), min(hi, s5.offset + s5.numel)
+        p, g = self._arena[lo:hi], self._garena[lo:hi]
+        m, v = self._adam_m[moff:moff + hi - lo], self._adam_v[moff:moff + hi - lo]
+        a, b = max(lo, s5.offset), min(hi, s5.offset + s5.numel)       # the part of linear5.weight inside this piece
+        sh = None
         if self._w5b is not None and self._w5b_version == self._w5_version() and a < b:
-            ops.adam_step_dev_shadow(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0],
-                                     self._w5b[a - s5.offset:b - s5.offset], a - lo, grad_scale, step_bias=1)
-        elif max_blocks:
-            ops.adam_step_dev_blocks(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], grad_scale, step_bias=1, max_blocks=max_blocks)
+            sh = self._w5b[a - s5.offset:b - s5.offset]
+        if guard is not None:
+            ops.adam_step_dev_guarded(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], guard, shadow=sh,
+                                      shadow_begin=(a - lo) if sh is not None else 0, grad_scale=grad_scale, step_bias=1)
+        elif sh is not None:
+            ops.adam_step_dev_shadow(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], sh, a - lo, grad_scale, step_bias=1)
         else:
             ops.adam_step_dev(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], grad_scale, step_bias=1)
 
@@ -1552,38 +1556,22 @@ class AVM(_LazyFlags, nn.Module):
             if _tick:
                 ops.counter_add(self._state[0], 1)
             return
+        pieces, off, cur = [], 0, 0                 # (lo, hi, offset of the moments)
         if _done:
             # ranges train_step already updated under backward (the early Adam on linear5.weight): the rest of the arena now
             assert segs == [(0, self._arena_numel)] and _guard is None
-            cur = 0
             for lo, hi in sorted(_done) + [(self._arena_numel, self._arena_numel)]:
                 if cur < lo:
-                    self._adam_range(cur, lo, lr, betas, eps, grad_scale)
+                    pieces.append((cur, lo, cur))
                 cur = hi
-            if _tick:
-                ops.counter_add(self._state[0], 1)
-            return
-        s5 = self.spec("visbl.linear5.weight")
-        shadow_ok = self._w5b is not None and self._w5b_version == self._w5_version()
-        off = 0
-        for lo, hi in segs:
-            cnt = hi - lo
-            p, g = self._arena[lo:hi], self._garena[lo:hi]
-            m, v = self._adam_m[off:off + cnt], self._adam_v[off:off + cnt]
-            off += cnt
-            a, b = max(lo, s5.offset), min(hi, s5.offset + s5.numel)       # the part of linear5.weight inside this segment
-            if _guard is not None:
-                # fp16: the same pass, skipped as a whole when this step's gradients overflowed (goalnet_grad_finite_check)
-                sh = self._w5b[a - s5.offset:b - s5.offset] if (shadow_ok and a < b) else None
-                ops.adam_step_dev_guarded(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], _guard, shadow=sh,
-                                          shadow_begin=(a - lo) if sh is not None else 0, grad_scale=grad_scale, step_bias=1)
-            elif shadow_ok and a < b:
-                # bf16 mode at > 16 rows: refresh the shadow of linear5.weight in the same pass (the kernels do not bump versions)
-                ops.adam_step_dev_shadow(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0],
-                                         self._w5b[a - s5.offset:b - s5.offset], a - lo, grad_scale, step_bias=1)
-            else:
-                ops.adam_step_dev(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], grad_scale, step_bias=1)
+        else:
+            for lo, hi in segs:
+                pieces.append((lo, hi, off))
+                off += hi - lo
+        for lo, hi, moff in pieces:
+            self._adam_piece(lo, hi, moff, lr, betas, eps, grad_scale, _guard)
         if len(segs) > 1:
+            shadow_ok = self._w5b is not None and self._w5b_version == self._w5_version()
             self.grad_sync.after_adam(self, self._w5b if shadow_ok else None)
         if _tick:
             ops.counter_add(self._state[0], 1)

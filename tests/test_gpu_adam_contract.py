@@ -99,7 +99,7 @@ def _slices(n):
 @pytest.mark.parametrize("which", range(4))
 def test_shadow_is_the_rounded_slice_and_nothing_else(n, which, dtype):
     """shadow == p_new[begin : begin + count].to(dtype) (round to nearest even) and every byte around it is untouched. p, g, m, v
-    are views at a non-zero 16-byte-aligned offset of larger arenas (as AVM._adam_range passes them); the arenas outside the views
+    are views at a non-zero 16-byte-aligned offset of larger arenas (as AVM._adam_piece passes them); the arenas outside the views
     keep their bits."""
     lib = _lib.load()
     begin, count = _slices(n)[which]

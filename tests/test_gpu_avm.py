@@ -486,10 +486,11 @@ def test_bf16_mode_on_frames_wider_than_the_fused_backward_serves():
 
 
 @pytest.mark.parametrize("precision", ["bf16x6", "fp16x3"])
-def test_backward_refuses_split_operands_a_second_forward_overwrote(precision):
+def test_backward_refuses_split_operands_a_second_forward_overwrote(precision, monkeypatch):
     """precision="bf16x6" / "fp16x3" at 13 frames of 224 x 224, the fewest at which conv2 and conv3 both run on split operands:
     backward reads the split activations the forward left in the cached padded buffers. A second training-mode forward
-    overwrites them; the backward of the first must raise, naming the model's precision, instead of using the wrong operands."""
+    overwrites them; the backward of the first must raise, naming the model's precision, instead of using the wrong operands — and
+    before its first launch."""
     n, h = 13, 224
     torch.manual_seed(5)
     model = AVM(audio_included=True, device=DEV, precision=precision, seed=synth.BASE_SEED)
@@ -498,6 +499,78 @@ def test_backward_refuses_split_operands_a_second_forward_overwrote(precision):
     _, ctx = model.forward_device(aud, vis, save=True)
     assert "x2s" in ctx, "conv3 did not run on split operands: the test would be vacuous"
     model.forward_device(aud, vis, save=True)
+    dout = torch.ones(n, device=DEV)
+    calls = _record_ops_calls(monkeypatch)
     with pytest.raises(RuntimeError, match=f"precision='{precision}'.*overwrote the saved split operands"):
-        model.backward_device(ctx, torch.ones(n, device=DEV))
+        model.backward_device(ctx, dout)
+    assert calls == [], f"refused after {len(calls)} launches: {calls[:4]}"
     torch.cuda.synchronize()
+
+
+def _record_ops_calls(monkeypatch):
+    """every public function of ops behind a recorder: the returned list holds the name of each call made from here on"""
+    import types
+    calls = []
+
+    def wrap(name, fn):
+        def wrapped(*a, **k):
+            calls.append(name)
+            return fn(*a, **k)
+        return wrapped
+    for name, fn in list(vars(ops).items()):
+        if isinstance(fn, types.FunctionType) and not name.startswith("_"):
+            monkeypatch.setattr(ops, name, wrap(name, fn))
+    return calls
+
+
+def test_backward_refusals_precede_the_first_launch(monkeypatch):
+    """precision="bf16", 10 frames of 40 x 40 (a forked step: its first launch is the weight flip on the side stream): the backward of a
+    ctx whose saved 16-bit operands a second forward overwrote is refused before anything is enqueued or allocated — no ops call, no
+    gradient arena, nothing pending on the side stream; the next forward + backward gives the bits of a fresh model's."""
+    import _freeze_case as FC
+    from _mode_case import fixture
+    fx = fixture("regression", True, "train", 10)
+    aud, vis = fx["aud"].to(DEV), fx["vis"].to(DEV)
+    dout = torch.ones(10, device=DEV)
+    m, fresh = FC.load_model(fx, precision="bf16"), FC.load_model(fx, precision="bf16")
+    _, ctx = m.forward_device(aud, vis, save=True)
+    m.forward_device(aud, vis, save=True)
+    calls = _record_ops_calls(monkeypatch)
+    with pytest.raises(RuntimeError, match="precision='bf16'.*overwrote the saved bf16 operands"):
+        m.backward_device(ctx, dout)
+    assert calls == [], calls
+    monkeypatch.undo()
+    assert m._garena is None
+    torch.cuda.synchronize()
+    outs = []
+    for k in (m, fresh):
+        out, ctx = k.forward_device(aud, vis, save=True)
+        k.backward_device(ctx, dout)
+        outs.append(out)
+    torch.cuda.synchronize()
+    assert m._side_stream is not None, "the step did not fork: the test would not see a pending side stream"
+    assert torch.equal(outs[0], outs[1]) and torch.equal(m._garena, fresh._garena)
+
+
+def test_an_inputs_only_backward_keeps_gemm_sized_gradients_out_of_scratch(monkeypatch):
+    """input_gradients trains nothing, so every parameter gradient a fused kernel cannot omit goes to the pass's scratch. The launches
+    that write a GEMM-sized gradient (conv2 / conv3 / linear5 weights) are issued for trained tensors only, so scratch is never asked
+    for one: it holds small tensors alone, and the arena is not even allocated."""
+    import _freeze_case as FC
+    from _mode_case import fixture
+    from cvml_goalnet_amd import avm
+    fx = fixture("regression", True, "train", 10)
+    m = FC.load_model(fx)
+    made, init = [], avm._Bwd.__init__
+
+    def spy(self, *a):
+        init(self, *a)
+        made.append(self)
+    monkeypatch.setattr(avm._Bwd, "__init__", spy)
+    d_aud, d_vis = m.input_gradients(fx["aud"], fx["vis"])
+    torch.cuda.synchronize()
+    (bwd,) = made
+    assert not bwd.train and "visbl.bnorm3.weight" in bwd.scratch and m._garena is None
+    assert d_vis.abs().max().item() > 0, "the data-gradient chain ran through conv3 and conv2"
+    for name in bwd.scratch:
+        assert m.spec(name).kind not in ("ohwi", "lin5"), f"scratch holds the GEMM-sized gradient of {name}"

@@ -343,3 +343,39 @@ def test_small_step_one_launch_kernels_match_the_multi_launch_forms(n, audio, mo
     d = (fused_m._arena - plain_m._arena).abs().max().item()
     assert d <= 2 * 2 * LR, f"parameters differ by {d}"
     assert torch.equal(fused_m._state[:2], plain_m._state[:2])
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16"])
+def test_a_refused_step_leaves_no_residue(precision):
+    """10 frames of 40 x 40: a train_step that forward_device refuses (audio of the wrong shape, before any launch) leaves nothing behind
+    on the model — the two good steps that follow equal a fresh model's two steps bit for bit, and the forward right after the refusal
+    ticks its dropout draw itself (the tick is not left to a caller that never comes)."""
+    import _freeze_case as FC
+    from _mode_case import fixture
+    fx = fixture("regression", True, "train", 10)
+    aud, vis, lab = fx["aud"].to(DEV), fx["vis"].to(DEV), fx["lab"].to(DEV)
+    bad_aud = torch.zeros(10, 29, 30, device=DEV)
+
+    def model():
+        m = FC.load_model(fx, True, precision)
+        m.dropout_mode = "device"                     # counter-based masks: a draw that is not ticked would repeat
+        return m
+
+    def two_steps(m):
+        out = [tuple(t.clone() for t in m.train_step(aud, vis, lab, lr=LR)) for _ in range(2)]
+        torch.cuda.synchronize()
+        return out
+
+    a, b, c = model(), model(), model()
+    for m in (a, c):
+        with pytest.raises(RuntimeError, match="audio_input must be"):
+            m.train_step(bad_aud, vis, lab, lr=LR)
+    draws = int(c._state[1])
+    with torch.no_grad():
+        c(aud, vis)
+    assert int(c._state[1]) == draws + 1, "the draw of the forward after a refused step was not ticked"
+    for s, ((la, pa), (lb, pb)) in enumerate(zip(two_steps(a), two_steps(b))):
+        assert torch.equal(la, lb) and torch.equal(pa, pb), f"step {s}"
+    for k in ("_arena", "_garena", "_state") + (("_guard",) if precision == "fp16" else ()):
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    assert int(a._state[1]) == 2, "each good step ticked its draw once"

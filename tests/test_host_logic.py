@@ -329,3 +329,56 @@ def test_split_operand_arithmetic_of_bf16x6_and_fp16x3_in_numpy():
     assert np.all(np.abs((Ah.astype(np.float64) + Am) - A)[big] <= 2.0 ** -22 * np.abs(A)[big])
     three = (Ah.astype(np.float64) * Bm + Am.astype(np.float64) * Bh + Ah.astype(np.float64) * Bh) / (sa * sb)
     assert np.all(np.abs(three - exact) <= 2.0 ** -20 * np.abs(a.astype(np.float64)) * np.abs(b.astype(np.float64)) + 2.0 ** -24 / (sa * sb) * 2.0 ** 15)   # (iii)
+
+
+def _routing(m):
+    """every routing decision of AVM that an A/B switch of DESIGN.md's table can move, at a shape where the default says yes"""
+    a = torch.zeros(1, 8, 8, 64)
+    return {"GOALNET_X6_OFF": (m.x6_off, m._x6_conv(70000, 256), m._x6_linear5(256, 512 * 70 * 70)),
+            "GOALNET_X6_LINEAR5": (m.x6_linear5, m._x6_linear5(256, 512 * 70 * 70)),
+            "GOALNET_MLP_FUSED": (m.mlp_fused, m._mlp_fused(10)),
+            "GOALNET_SMALL_BN": (m.small_bn, m._small_bn(a, a, 1, 8, 8, 64)),
+            "GOALNET_X3_WGRAD2": (m.x3_wgrad2,),
+            "GOALNET_X3_DGRAD2": (m.x3_dgrad2,),
+            "GOALNET_FORCE_BF5": (m.force_bf5, m._bf5(10)),
+            "GOALNET_OVERLAP_PAIR": (m.overlap_pair, m._pair(256)),
+            "GOALNET_OVERLAP_LARGE": (m.overlap_large, m.overlap_auto, m._large_overlap(10), m._fork_ok(100))}
+
+
+# variable -> (the value that moves it off its default, _routing's answer by default, and with that value)
+SWITCHES = {"GOALNET_X6_OFF": ("1", (False, True, True), (True, False, False)),
+            "GOALNET_X6_LINEAR5": ("0", (True, True), (False, False)),
+            "GOALNET_MLP_FUSED": ("0", (True, True), (False, False)),
+            "GOALNET_SMALL_BN": ("0", (True, True), (False, False)),
+            "GOALNET_X3_WGRAD2": ("0", (True,), (False,)),
+            "GOALNET_X3_DGRAD2": ("0", (True,), (False,)),
+            "GOALNET_FORCE_BF5": ("1", (False, False), (True, True)),
+            "GOALNET_OVERLAP_PAIR": ("0", (True, True), (False, False)),
+            "GOALNET_OVERLAP_LARGE": ("1", (False, True, False, False), (True, False, True, True))}
+
+
+@pytest.mark.parametrize("var", sorted(SWITCHES))
+def test_routing_switches_are_read_when_the_model_is_constructed(var, monkeypatch):
+    """A graph captured from a step bakes the routing in, so a switch must not be able to change between two steps of one model: the
+    value set BEFORE construction decides the attribute and the predicate, one set or unset afterwards moves neither."""
+    value, by_default, switched = SWITCHES[var]
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    precision = "bf16" if var in ("GOALNET_FORCE_BF5", "GOALNET_OVERLAP_PAIR") else "bf16x6"
+    m = AVM(True, precision=precision)
+    assert _routing(m)[var] == by_default
+    monkeypatch.setenv(var, value)
+    assert _routing(m)[var] == by_default, "changed after construction: the model must not follow"
+    m2 = AVM(True, precision=precision)
+    assert _routing(m2)[var] == switched
+    monkeypatch.delenv(var)
+    assert _routing(m2)[var] == switched, "unset after construction: the model must not follow"
+    other = {k: v for k, v in _routing(m2).items() if k != var and not {k, var} <= {"GOALNET_X6_OFF", "GOALNET_X6_LINEAR5"}}
+    assert other == {k: v for k, v in _routing(m).items() if k in other}, "a switch moved a decision that is not its own"
+
+
+def test_a_step_keeps_no_transient_state_on_the_model():
+    """what a step's routines hand to each other travels as arguments, in ctx and in the backward pass's own holder"""
+    m = AVM(True)
+    for k in ("_defer_tick", "_pending_drop_tick", "_fused_loss", "_fused_loss_done", "_fork", "_dbias_pending", "_scratch_grads", "_adam_stream"):
+        assert not hasattr(m, k), k

@@ -12,6 +12,7 @@
 // 2 x 2 MFMA tiles of 32 x 32 (64 accumulator VGPRs). Operands are staged global -> registers -> LDS
 // (the A loader applies an affine and zero padding on the way, so LDS-DMA is not usable), double-buffered
 // in LDS with the next K-tile's global loads in flight under the current tile's 64 MFMAs per wave.
+// (The convolution's A operand is staged once per nine K-tiles where its strip fits: ConvAStripLoader.)
 // An fp32 MFMA occupies its SIMD for 64 cycles, so the 4096 MFMA cycles per K-tile per wave cover the
 // 8 global loads + 8 LDS writes + 16-32 LDS reads a thread issues per K-tile with room to spare.
 //
@@ -86,6 +87,7 @@ struct KCLoader {
         int convC;
     };
     static constexpr bool KC = true;
+    static constexpr bool STRIP = false;
     static constexpr bool ONE_STAGE = false;      // as the A operand (linear5 forward / dX): two LDS stages, see launch_gemm
     static constexpr int ONE_STAGE_BLOCKS = 3;
     __amdgpu_buffer_rsrc_t rx, rsc, rsh;
@@ -139,6 +141,7 @@ struct MCLoader {
         const float* scale; const float* shift; int bnC;
     };
     static constexpr bool KC = false;
+    static constexpr bool STRIP = false;
     static constexpr bool ONE_STAGE = true;
 #ifndef GN_MC_BLOCKS
 #define GN_MC_BLOCKS 4
@@ -185,6 +188,23 @@ struct MCLoader {
     }
 };
 
+// bit kh * 3 + kw: tap (kh, kw) of output pixel m = (n,h,w) lies inside its frame; 0 for rows past M
+__device__ __forceinline__ unsigned conv_tap_mask(int64_t m, int64_t M, int H, int W) {
+    unsigned mk = 0;
+    if (m < M) {
+        const int w = (int)((unsigned)m % (unsigned)W);
+        const int h = (int)(((unsigned)m / (unsigned)W) % (unsigned)H);
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const bool v = (unsigned)(h + kh - 1) < (unsigned)H && (unsigned)(w + kw - 1) < (unsigned)W;
+                mk |= (v ? 1u : 0u) << (kh * 3 + kw);
+            }
+    }
+    return mk;
+}
+
 // im2col of an NHWC tensor for a 3x3 / stride 1 / pad 1 convolution: row m = (n,h,w), k = (kh,kw,ci).
 // The affine (BatchNorm of the producing block) is applied to in-bounds elements only: the reference pads the
 // BatchNorm OUTPUT with zeros (/root/reference/utils.py:154-156). The resource starts W+1 pixels in front of the
@@ -196,6 +216,7 @@ struct ConvALoader {
         const float* scale; const float* shift;
     };
     static constexpr bool KC = true;
+    static constexpr bool STRIP = false;
     static constexpr bool ONE_STAGE = true;
     static constexpr int ONE_STAGE_BLOCKS = AFFINE ? 3 : 4;      // with the affine the loop spills at a budget of 128 registers (111 TF/s)
     __amdgpu_buffer_rsrc_t rx, rsc, rsh;
@@ -215,20 +236,7 @@ struct ConvALoader {
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int64_t m = (int64_t)row0 + rr + 32 * i;
-            unsigned mk = 0;
-            if (m < p.M) {
-                const int w = (int)((unsigned)m % (unsigned)p.W);
-                const int h = (int)(((unsigned)m / (unsigned)p.W) % (unsigned)p.H);
-#pragma unroll
-                for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) {
-                        const bool v = (unsigned)(h + kh - 1) < (unsigned)p.H && (unsigned)(w + kw - 1) < (unsigned)p.W;
-                        mk |= (v ? 1u : 0u) << (kh * 3 + kw);
-                    }
-            }
-            mask[i] = mk;
+            mask[i] = conv_tap_mask((int64_t)row0 + rr + 32 * i, p.M, p.H, p.W);
         }
     }
     // K order = (32-channel chunk, tap): the nine taps of a chunk re-read the same 128-B lines (one pixel's chunk = one line)
@@ -256,6 +264,100 @@ struct ConvALoader {
         if (AFFINE) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) r[i] = f4sel((vmask >> i) & 1u, f4fma(r[i], sc, sh));
+        }
+    }
+};
+
+// The same operand staged once per 32-channel chunk instead of once per K-tile. The nine K-tiles (taps) of a chunk hold the
+// same input pixels shifted by kh * W + kw rows: all nine are windows of one strip of 128 + 2 (W + 1) consecutive pixels,
+// [row0 - (W + 1), row0 + 128 + (W + 1)). The block loads that strip once (buffer loads; pixels outside the tensor read 0
+// through an out-of-range voffset), applies the affine once per element and writes it to ONE K-contiguous LDS image of 128-B
+// rows, swizzled by kc_off on the strip row. K-tile (chunk, tap) then reads its A fragments from strip row
+// local_row + kh * W + kw. A lane whose (pixel, tap) is padding (frame border, or a row >= M) reads the row of zeros behind
+// the strip instead: an ADDRESS select by the same 9-bit tap masks, no data select and no affine in the loop.
+//   * bank conflicts: the 16 lanes of a ds_read_b128 group read rows whose residues mod 16 are all distinct ({0-3,12-15,
+//     20-27} + ...); (row & 1, (row >> 1) & 7) is that residue, it picks the 32-bank half and the swizzled 4-bank slot, and a
+//     constant row shift permutes residues. So every tap's window is conflict-free; only lanes sent to the zero row share
+//     one address (a broadcast) that may collide with a single data lane.
+//   * strip pixels of OTHER frames (and, with the affine, out-of-tensor rows holding `shift`) sit in the image but are only
+//     ever addressed by taps that the masks send to the zero row.
+//   * the loads of the next chunk's strip are issued one per tap under the current chunk's nine K-tiles, held in registers
+//     (9 float4) and written after the last tap's barrier; B (the weights) is staged per K-tile as before.
+// 32 strip rows per load and thread: 9 loads cover 288 rows, i.e. W <= 79; 289 rows of 128 B + 16 KB of B = 52.1 KB, three
+// blocks per CU.
+constexpr int STRIP_LOADS = 9;
+constexpr int STRIP_ROWS = 32 * STRIP_LOADS;                 // the row behind them (index STRIP_ROWS) holds zeros
+constexpr int STRIP_FLOATS = (STRIP_ROWS + 1) * BK;
+constexpr int CONV_STRIP_MAX_W = (STRIP_ROWS - BM) / 2 - 1;  // 128 + 2 (W + 1) <= 288
+
+template <bool AFFINE>
+struct ConvAStripLoader {
+    using P = typename ConvALoader<AFFINE>::P;
+    static constexpr bool KC = true;
+    static constexpr bool STRIP = true;
+    static constexpr bool ONE_STAGE = true;
+    static constexpr int ONE_STAGE_BLOCKS = 3;
+    __amdgpu_buffer_rsrc_t rx, rsc, rsh;
+    unsigned mask[2];        // tap masks of the two fragment rows this lane reads
+    unsigned lrow[2];        // their local rows in the tile
+    unsigned voff, vaff, bad;
+    int W, C, h;
+    float4 sc, sh;
+    __device__ ConvAStripLoader(const P& p, int row0, int tid) {
+        W = p.W; C = p.C;
+        const int c4 = (tid & 7) * 4, rr = tid >> 3;
+        const int64_t lead = (int64_t)row0 - (p.W + 1);
+        const int nrows = BM + 2 * (p.W + 1);
+        rx = make_rsrc(p.x + lead * p.C, (uint32_t)(nrows * p.C * 4));
+        voff = (unsigned)((rr * p.C + c4) * 4);
+        bad = 0;            // bit i: strip row rr + 32 i lies outside the tensor (or behind the strip): never touch it
+#pragma unroll
+        for (int i = 0; i < STRIP_LOADS; ++i) {
+            const int64_t pix = lead + rr + 32 * i;
+            bad |= (pix < 0 || pix >= p.M || rr + 32 * i >= nrows ? 1u : 0u) << i;
+        }
+        if (AFFINE) {
+            rsc = make_rsrc(p.scale, (uint32_t)p.C * 4);
+            rsh = make_rsrc(p.shift, (uint32_t)p.C * 4);
+            vaff = (unsigned)(c4 * 4);
+        }
+        const int wm = tid >> 7, r = tid & 31;
+        h = (tid >> 5) & 1;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            lrow[q] = (unsigned)(wm * 64 + q * 32 + r);
+            mask[q] = conv_tap_mask((int64_t)row0 + lrow[q], p.M, p.H, p.W);
+        }
+    }
+    __device__ __forceinline__ void begin(int chunk) {       // the chunk's affine coefficients (consumed by store())
+        if (AFFINE) {
+            sc = bload(rsc, vaff, (unsigned)(chunk * BK) * 4);
+            sh = bload(rsh, vaff, (unsigned)(chunk * BK) * 4);
+        }
+    }
+    __device__ __forceinline__ float4 load(int chunk, int i) const {
+        unsigned b = bad;                   // as in frag_base: nine hoisted voffsets would spill
+        asm volatile("" : "+v"(b));
+        return bload(rx, (b >> i) & 1u ? OOB : voff, (unsigned)((i * 32 * C + chunk * BK) * 4));
+    }
+    __device__ __forceinline__ void store(float* l, const float4 (&rs)[STRIP_LOADS], int tid) const {
+        const int c = tid & 7, row = tid >> 3;
+#pragma unroll
+        for (int i = 0; i < STRIP_LOADS; ++i)
+            *reinterpret_cast<float4*>(&l[kc_off(row + 32 * i, c)]) = AFFINE ? f4fma(rs[i], sc, sh) : rs[i];
+    }
+    // byte offsets of this lane's two fragment rows for K-tile `tap`; group s of the K-tile is at (offset ^ (s << 5)):
+    // kc_off(row, 2 s + h) * 4 = (row << 7 | (h ^ (row >> 1 & 7)) << 4) ^ (s << 5)
+    __device__ __forceinline__ void frag_base(int tap, unsigned (&ab)[2]) const {
+        const int kh = tap / 3, kw = tap - 3 * kh;
+        const unsigned shift = (unsigned)(kh * W + kw);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            // recomputed per K-tile (7 VALU): hoisted out of the chunk loop the 72 offsets of the nine taps spill
+            unsigned mk = mask[q];
+            asm volatile("" : "+v"(mk));
+            const unsigned row = (mk >> tap) & 1u ? lrow[q] + shift : (unsigned)STRIP_ROWS;
+            ab[q] = (row << 7) | (((unsigned)h ^ ((row >> 1) & 7u)) << 4);
         }
     }
 };
@@ -466,6 +568,74 @@ __device__ __forceinline__ void compute_tile(const float* la, const float* lb, f
     }
 }
 
+// One K-tile of the strip form: A fragments from the strip rows frag_base() picked for this tap, B as in compute_tile; the
+// same MFMA sequence per accumulator as compute_tile.
+template <bool BKC>
+__device__ __forceinline__ void compute_tile_strip(const float* ls, const float* lb, f32x16 (&acc)[2][2],
+                                                   const unsigned (&ab)[2], int wn, int r, int h) {
+    static_assert(BKC, "K-contiguous B image");
+    // B the same way (two offsets instead of eight loop-invariant addresses: the register budget of three blocks per CU)
+    const unsigned bb = (unsigned)kc_off(wn * 64 + r, h) * 4;     // row + 32: the same swizzle, 4 KB further
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        float a[2][4], b[2][4];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(ls) + (ab[q] ^ (unsigned)(s << 5)));
+            a[q][0] = t.x; a[q][1] = t.y; a[q][2] = t.z; a[q][3] = t.w;
+            const float4 u = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(lb) + ((bb ^ (unsigned)(s << 5)) + q * 32 * BK * 4));
+            b[q][0] = u.x; b[q][1] = u.y; b[q][2] = u.z; b[q][3] = u.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+                for (int fn = 0; fn < 2; ++fn)
+                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[fm][j], b[fn][j], acc[fm][fn], 0, 0, 0);
+        }
+    }
+}
+
+// Main loop of the strip form (ConvAStripLoader, no split-K: K-tiles 0 .. 9 chunks - 1): one strip image, one B stage.
+template <class AL, class BL>
+__device__ __forceinline__ void conv_strip_loop(AL& al, BL& bl, float* ls, float* lb, f32x16 (&acc)[2][2], int ktiles,
+                                                int tid, int wn, int r, int h) {
+    float4 rs[STRIP_LOADS], rb[4];
+    const int nchunks = ktiles / 9;
+    if (tid < 8) *reinterpret_cast<float4*>(&ls[STRIP_ROWS * BK + tid * 4]) = f4zero();
+    al.begin(0);
+#pragma unroll
+    for (int i = 0; i < STRIP_LOADS; ++i) rs[i] = al.load(0, i);
+    bl.issue(0, rb);
+    al.store(ls, rs, tid);
+    bl.finish(rb);
+    store_tile<BL::KC>(lb, rb, tid);
+    __syncthreads();
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+        const bool next = chunk + 1 < nchunks;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const bool more = tap < 8 || next;
+            if (more) bl.issue(chunk * 9 + tap + 1, rb);
+            if (next) rs[tap] = al.load(chunk + 1, tap);  // one load of the next chunk's strip per tap, held until tap 8
+            unsigned ab[2];
+            al.frag_base(tap, ab);
+            compute_tile_strip<BL::KC>(ls, lb, acc, ab, wn, r, h);
+            __syncthreads();                              // every wave has read the B stage (and, at tap 8, the strip)
+            if (more) {
+                bl.finish(rb);
+                store_tile<BL::KC>(lb, rb, tid);
+            }
+            if (tap == 8 && next) {
+                al.begin(chunk + 1);                      // only now: rb's registers are free for the coefficients
+                al.store(ls, rs, tid);
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // ---- narrow outputs (N <= 64: conv2's data gradient has 64 output channels) -------------------------------------------------
 // On the 128-wide tile half of every MFMA multiplied zero columns (measured: 66 TF/s of useful work). N64: the block tile is
 // 128 x 64 — the four waves stack along M (32 rows each) and every wave computes 32 x 64 = 1 x 2 MFMA tiles; the LDS images and
@@ -518,11 +688,16 @@ __device__ __forceinline__ void store_acc_n64(const EpiP& ep, const f32x16 (&acc
 // Round 2: a two-deep register prefetch for the weight gradient (loads of K-tile kt + 2 issued before the MFMAs of tile kt,
 // two register sets and loader instances alternating; 248 VGPRs, no spill) measured 116.4 vs 116.6 TF/s at 128 frames:
 // memory latency is not what holds it at 0.69-0.74 of peak either. Removed.
+// Kept: the strip A loader of the 3x3 convolution (ConvAStripLoader, `if constexpr (AL::STRIP)` below). It does not move the
+// same bytes differently, it moves fewer: the nine K-tiles of a channel chunk are windows of one pixel strip, staged once
+// (A bytes into LDS 144 -> 36 KB per chunk and block, the affine once per element, no select). 1024 frames, alternating in one
+// process (scripts/bench_conv_strip.py, profiles/conv_strip_kernel_stats.md): conv3 forward 92.9 -> 88.0 ms (134.8 -> 142.2
+// TF/s), conv3 data gradient 90.0 -> 86.5 (139.2 -> 144.8; three blocks per CU instead of four), conv2 forward 13.56 -> 12.54
+// (122.0 -> 131.9); outputs bit-identical.
 template <class AL, class BL, bool N64 = false, int STAGES = 2>
 __global__ __launch_bounds__(256, STAGES == 1 ? (N64 ? 4 : AL::ONE_STAGE_BLOCKS) : 2) void gemm_f32_kernel(typename AL::P ap, typename BL::P bp, EpiP ep,
                                                           int tiles_m, int tiles_n, int m_fast,
                                                           int ktiles, int ktiles_per_split, int xcd_splits) {
-    __shared__ __attribute__((aligned(16))) float lds[STAGES][2][OP_FLOATS];
     const int tid = threadIdx.x;
     int tm, tn, split;
     if (xcd_splits > 0) {
@@ -571,34 +746,42 @@ __global__ __launch_bounds__(256, STAGES == 1 ? (N64 ? 4 : AL::ONE_STAGE_BLOCKS)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    float4 ra[4], rb[4];
-    if (kt0 < kt1) {
-        al.issue(kt0, ra);
-        bl.issue(kt0, rb);
-        al.finish(ra);
-        bl.finish(rb);
-        store_tile<AL::KC>(lds[0][0], ra, tid);
-        store_tile<BL::KC>(lds[0][1], rb, tid);
-    }
-    __syncthreads();
-    for (int kt = kt0; kt < kt1; ++kt) {
-        const int cur = STAGES == 1 ? 0 : (kt - kt0) & 1;
-        const bool more = kt + 1 < kt1;
-        if (more) {
-            // the buffer being filled was last read in iteration kt-1, which every wave left through the barrier
-            al.issue(kt + 1, ra);
-            bl.issue(kt + 1, rb);
-        }
-        if constexpr (N64) compute_tile_n64(lds[cur][0], lds[cur][1], acc[0], wave, r, h);
-        else compute_tile<AL::KC, BL::KC>(lds[cur][0], lds[cur][1], acc, wm, wn, r, h);
-        if constexpr (STAGES == 1) __syncthreads();      // one LDS stage (32 KB: three blocks per CU): every wave has read it
-        if (more) {
+    if constexpr (AL::STRIP) {
+        static_assert(!N64 && STAGES == 1 && BL::KC, "the strip form: 128 x 128 tile, one B stage");
+        __shared__ __attribute__((aligned(16))) float lstrip[STRIP_FLOATS];
+        __shared__ __attribute__((aligned(16))) float lbs[OP_FLOATS];
+        conv_strip_loop(al, bl, lstrip, lbs, acc, kt1 - kt0, tid, wn, r, h);
+    } else {
+        __shared__ __attribute__((aligned(16))) float lds[STAGES][2][OP_FLOATS];
+        float4 ra[4], rb[4];
+        if (kt0 < kt1) {
+            al.issue(kt0, ra);
+            bl.issue(kt0, rb);
             al.finish(ra);
             bl.finish(rb);
-            store_tile<AL::KC>(lds[STAGES == 1 ? 0 : cur ^ 1][0], ra, tid);
-            store_tile<BL::KC>(lds[STAGES == 1 ? 0 : cur ^ 1][1], rb, tid);
+            store_tile<AL::KC>(lds[0][0], ra, tid);
+            store_tile<BL::KC>(lds[0][1], rb, tid);
         }
         __syncthreads();
+        for (int kt = kt0; kt < kt1; ++kt) {
+            const int cur = STAGES == 1 ? 0 : (kt - kt0) & 1;
+            const bool more = kt + 1 < kt1;
+            if (more) {
+                // the buffer being filled was last read in iteration kt-1, which every wave left through the barrier
+                al.issue(kt + 1, ra);
+                bl.issue(kt + 1, rb);
+            }
+            if constexpr (N64) compute_tile_n64(lds[cur][0], lds[cur][1], acc[0], wave, r, h);
+            else compute_tile<AL::KC, BL::KC>(lds[cur][0], lds[cur][1], acc, wm, wn, r, h);
+            if constexpr (STAGES == 1) __syncthreads();      // one LDS stage (32 KB: three blocks per CU): every wave has read it
+            if (more) {
+                al.finish(ra);
+                bl.finish(rb);
+                store_tile<AL::KC>(lds[STAGES == 1 ? 0 : cur ^ 1][0], ra, tid);
+                store_tile<BL::KC>(lds[STAGES == 1 ? 0 : cur ^ 1][1], rb, tid);
+            }
+            __syncthreads();
+        }
     }
     if constexpr (N64) store_acc_n64(ep, acc[0], tm, tn, split, wave, r, h);
     else store_acc<!AL::KC, !BL::KC>(ep, acc, tm, tn, split, wm, wn, r, h);
@@ -692,16 +875,18 @@ int launch_gemm(const char* name, const typename AL::P& ap, const typename BL::P
     // 91.3 -> 96.1; linear5 forward 121.9 -> 99.7 and dX 116.4 -> 114.7 (a K-contiguous A operand with a 10 MB row stride): by
     // the A loader's trait. GOALNET_F32_STAGES=1|2 forces one form (tests, A/B runs).
     static const int force_stages = getenv("GOALNET_F32_STAGES") ? atoi(getenv("GOALNET_F32_STAGES")) : 0;
-    const bool one_stage = force_stages == 1 || (force_stages != 2 && AL::ONE_STAGE);
+    const bool one_stage = AL::STRIP || force_stages == 1 || (force_stages != 2 && AL::ONE_STAGE);     // the strip form has no two-stage variant
     if (one_stage) {        // the 128 x 64 tile as well: conv2's data gradient 108.9 -> 123.1 TF/s
         hipLaunchKernelGGL((gemm_f32_kernel<AL, BL, N64, 1>), grid, dim3(256), 0, st, ap, bp, ep, (int)tiles_m, (int)tiles_n,
                            m_fast, ktiles, kps, xcd_local ? nsplit : 0);
         GN_LAUNCH_CHECK(name);
         return 0;
     }
-    hipLaunchKernelGGL((gemm_f32_kernel<AL, BL, N64>), grid, dim3(256), 0, st, ap, bp, ep, (int)tiles_m, (int)tiles_n,
-                       m_fast, ktiles, kps, xcd_local ? nsplit : 0);
-    GN_LAUNCH_CHECK(name);
+    if constexpr (!AL::STRIP) {
+        hipLaunchKernelGGL((gemm_f32_kernel<AL, BL, N64>), grid, dim3(256), 0, st, ap, bp, ep, (int)tiles_m, (int)tiles_n,
+                           m_fast, ktiles, kps, xcd_local ? nsplit : 0);
+        GN_LAUNCH_CHECK(name);
+    }
     return 0;
 }
 
@@ -749,6 +934,17 @@ static int conv_splits_f32(int64_t M, int Cin, int Cout) {
     return conv_fwd_splits(((M + BM - 1) / BM) * ((Cout + BN - 1) / BN), 9 * Cin / BK);
 }
 
+// The strip A loader (ConvAStripLoader) serves a call when there is no split-K (it walks whole chunks), the strip fits
+// its LDS image (W <= 79), the tile is 128 x 128 and the role is one where it measured faster: both did
+// (profiles/conv_strip_kernel_stats.md). GOALNET_F32_CONV_STRIP=0, read per call, forces the per-tap loader (tests, A/B runs).
+constexpr bool CONV_STRIP_FWD = true;        // with the affine: the forward
+constexpr bool CONV_STRIP_DGRAD = true;      // without: the data gradient on flipped weights
+static bool conv_strip_f32(int W, int nsplit, bool narrow, bool affine) {
+    const char* e = getenv("GOALNET_F32_CONV_STRIP");
+    if (e && e[0] == '0') return false;
+    return nsplit == 1 && !narrow && W <= CONV_STRIP_MAX_W && (affine ? CONV_STRIP_FWD : CONV_STRIP_DGRAD);
+}
+
 size_t goalnet_conv3x3_fwd_ws_bytes(int N, int H, int W, int Cin, int Cout) {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
     const int64_t M = (int64_t)N * H * W;
@@ -787,8 +983,15 @@ int goalnet_conv3x3_fwd(const float* x, const float* scale, const float* shift, 
         ep = efinal;
         ep.slabs = (float*)ws; ep.slab_stride = M * Cout; ep.tile_ctr = tile_ctr;
     }
+    const bool strip = conv_strip_f32(W, nsplit, narrow, scale != nullptr);
     int rc;
-    if (scale) {
+    if (strip && scale) {
+        ConvAStripLoader<true>::P ap{x, H, W, Cin, M, scale, shift};
+        rc = launch_gemm<ConvAStripLoader<true>, KCLoader<false>>("conv3x3_fwd", ap, bp, ep, M, Cout, ktiles, 1, 0, st);
+    } else if (strip) {
+        ConvAStripLoader<false>::P ap{x, H, W, Cin, M, nullptr, nullptr};
+        rc = launch_gemm<ConvAStripLoader<false>, KCLoader<false>>("conv3x3_fwd", ap, bp, ep, M, Cout, ktiles, 1, 0, st);
+    } else if (scale) {
         ConvALoader<true>::P ap{x, H, W, Cin, M, scale, shift};
         rc = narrow ? launch_gemm<ConvALoader<true>, KCLoader<false>, true>("conv3x3_fwd", ap, bp, ep, M, Cout, ktiles, nsplit, 0, st)
                     : launch_gemm<ConvALoader<true>, KCLoader<false>>("conv3x3_fwd", ap, bp, ep, M, Cout, ktiles, nsplit, 0, st);
@@ -808,7 +1011,7 @@ template <class AL, class BL, bool N64, int STAGES> const char* gemm_f32_kernel_
 // as launch_gemm dispatches: one LDS stage by the A loader's trait, GOALNET_F32_STAGES forces one form
 template <class AL, class BL, bool N64> const char* gemm_f32_kernel_name() {
     const int force = getenv("GOALNET_F32_STAGES") ? atoi(getenv("GOALNET_F32_STAGES")) : 0;
-    const bool one = force == 1 || (force != 2 && AL::ONE_STAGE);
+    const bool one = AL::STRIP || force == 1 || (force != 2 && AL::ONE_STAGE);
     return one ? gemm_f32_kernel_name_<AL, BL, N64, 1>() : gemm_f32_kernel_name_<AL, BL, N64, 2>();
 }
 }
@@ -817,8 +1020,11 @@ extern "C" {
 /* which kernel goalnet_conv3x3_fwd launches for these dims (the dispatch above, not executed): bench.py names its roofline
  * kernel from this instead of a hard-coded string */
 const char* goalnet_conv3x3_fwd_kernel_name(int N, int H, int W, int Cin, int Cout, int affine) {
-    (void)N; (void)H; (void)W; (void)Cin;
     const bool narrow = Cout <= 64 && !getenv("GOALNET_F32_N64_OFF");       // as in goalnet_conv3x3_fwd
+    const int nsplit = (N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0) ? conv_splits_f32((int64_t)N * H * W, Cin, Cout) : 1;
+    if (conv_strip_f32(W, nsplit, narrow, affine != 0))
+        return affine ? gemm_f32_kernel_name<ConvAStripLoader<true>, KCLoader<false>, false>()
+                      : gemm_f32_kernel_name<ConvAStripLoader<false>, KCLoader<false>, false>();
     if (affine) return narrow ? gemm_f32_kernel_name<ConvALoader<true>, KCLoader<false>, true>() : gemm_f32_kernel_name<ConvALoader<true>, KCLoader<false>, false>();
     return narrow ? gemm_f32_kernel_name<ConvALoader<false>, KCLoader<false>, true>() : gemm_f32_kernel_name<ConvALoader<false>, KCLoader<false>, false>();
 }

@@ -188,8 +188,9 @@ struct ConvAPadLoaderH {
         const int n0 = fast_div(row0, inv_hw), r0 = row0 - n0 * hw, h0 = fast_div(r0, inv_w), w0 = r0 - h0 * p.W;
         const int64_t pm0 = ((int64_t)n0 * (p.H + 2) + h0 + 1) * Wp2 + w0 + 1;      // padded index of the tile's first pixel
         const int G = Wp2 + 1;
-        // a tile of 128 consecutive output pixels spans < 128 + 2 * (rows crossed + frames crossed * (W+2)) padded pixels
-        rx = make_rsrc(p.x + (pm0 - G) * p.C, (uint32_t)((BM + 2 * (BM / p.W + 2) + 4 * Wp2 + 2 * G) * p.C * 2));
+        // a tile of 128 consecutive output pixels spans < 128 + 2 * (rows crossed + frames crossed * (W+2)) padded pixels; it crosses
+        // up to BM / (H W) + 1 frames (frames of fewer than 64 pixels: more than two — a budget of two cut the tile's last rows off)
+        rx = make_rsrc(p.x + (pm0 - G) * p.C, (uint32_t)((BM + 2 * (BM / p.W + 2) + 2 * Wp2 * (BM / hw + 2) + 2 * G) * p.C * 2));
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int rl = (wave * 4 + i) * 8 + (lane >> 3);

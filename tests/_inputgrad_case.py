@@ -34,6 +34,13 @@ CELLS = (
     Cell("fp32", "regression", False, "train", 10),
 )
 
+# two of them on frames with H != W (tests/_mode_case.py: SHAPE_CELLS): conv1's data gradient with another remainder along each axis
+# (41 % 3 = 2, 52 % 3 = 1) and d_visual returned as (N, 3, H, W) on a frame taller than wide, under the fp32 and the bf16 chain
+SHAPE_CELLS = (
+    Cell("fp32", "regression", False, "train", 10, (41, 52)),
+    Cell("bf16", "regression", True, "train", 10, (64, 40)),
+)
+
 
 def weights_of(c, classes=5):
     """frame weights linspace(0.5, 1.5, N) — for the classifier head (N, C), every class with its own sign and size"""

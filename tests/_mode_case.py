@@ -1,6 +1,7 @@
 """One fused step of ANY mode against the CPU oracle: what tests/test_gpu_bench_shapes.py::_run_case does with copies = 1, generalised to
 `head`, `audio_included` and train / eval mode, at 40 x 40 frames, bins = 30 and n in {10, 32} (n = 10: the skinny linear5, the fused MLP
-of the regression head, the one-launch BatchNorm kernels; n = 32: the 16-bit linear5 / p3 / y3 and the unfused MLP).
+of the regression head, the one-launch BatchNorm kernels; n = 32: the 16-bit linear5 / p3 / y3 and the unfused MLP). SHAPE_CELLS runs five
+of the cells again on four frames with H != W, where the host code's (h, w) bookkeeping can be wrong without a square frame noticing.
 
 Three parts, so that the comparison can be run — and broken on purpose — without a GPU (tests/test_mode_matrix_host.py):
 
@@ -36,7 +37,7 @@ from test_gpu_avm import _is_reduction_grad
 from test_gpu_bench_shapes import F32_FACTOR, TOL16, _gates_first, _mlp_gates_first, _taps_first
 
 DEV = "cuda:0"
-H = 40
+HW = (40, 40)             # the frame of the committed mode matrix; SHAPE_CELLS below carries its own
 LR = 1e-3
 CLASS_GAP = 4e-5          # fp32 cells: classes are compared on rows whose oracle top-2 score gap exceeds 2 x the 2e-5 score tolerance
 GUARD_GRADS = ("visbl.conv3.weight", "visbl.linear5.weight")
@@ -44,7 +45,7 @@ GUARD_GRADS = ("visbl.conv3.weight", "visbl.linear5.weight")
 # tells a row of the classifier's loss from another: swapping the two frames would be a symmetry of the step, invisible in every gradient
 LABEL_SEED = synth.BASE_SEED + 1
 
-Cell = namedtuple("Cell", "precision head audio mode n")
+Cell = namedtuple("Cell", "precision head audio mode n hw", defaults=(HW,))
 
 # precision x head x audio x mode x n: every combination of levels of any three factors appears (asserted by
 # tests/test_mode_matrix_host.py). Written out by hand; nothing is generated at run time.
@@ -67,9 +68,62 @@ CELLS = (
     Cell("fp32", "regression", True, "train", 10),
 )
 
+# ---- frames with H != W ------------------------------------------------------------------------------------------------------------
+# On a square frame an hc handed over where wc belongs, a width predicate evaluated on the height or a buffer sized (w, h) computes the
+# same numbers. Four shapes; conv-output sizes (hc, wc) of y1, y2, y3 and the pooled p3, written by hand from (h + 3) // 3 + 1 and three
+# times "- 2" (tests/test_mode_matrix_host.py holds the table against AVM._sizes):
+#   (40, 64)  wide: at n = 10 block 3 is above ops.SMALL_BN_ELEMS (10 * 11 * 19 * 512 = 1 070 080 > 2^20), blocks 1 and 2 below it,
+#             while linear5 (skinny) and the fused MLP still run: no square cell has that combination
+#   (64, 40)  its transpose: a fault that is symmetric under H <-> W cannot pass both
+#   (41, 52)  H % 3 = 2, W % 3 = 1: conv1's last stride-3 window is cut differently along each axis
+#   (40, 16)  the narrowest frame the model takes: conv3 on 3-pixel rows, p3 one pixel wide, K5 = 4 608; all three blocks stay on the
+#             one-launch BatchNorm kernels even at n = 32, where linear5 is on the MFMA path and the MLP unfused
+SHAPE_GEOMETRY = {
+    (40, 64): ((15, 23), (13, 21), (11, 19), (9, 17)),
+    (64, 40): ((23, 15), (21, 13), (19, 11), (17, 9)),
+    (41, 52): ((15, 19), (13, 17), (11, 15), (9, 13)),
+    (40, 16): ((15, 7), (13, 5), (11, 3), (9, 1)),
+}
+
+# (cell, launches of (ops.pool_bn_fwd_small, ops.pool_bnstats_fwd, ops.pool_bn_eval_fwd) in its forward). The counts are derived by hand
+# from the table above and the documented rule — a train-mode block takes the one-launch kernel when its conv output and its pooled
+# activation are fp32 tensors, c <= 512 and n * hc * wc * c <= 2^20; every eval-mode block takes pool_bn_eval_fwd:
+#   elements of y1 / y2 / y3 (c = 64 / 256 / 512) per frame:  40x64 and 64x40: 22 080 / 69 888 / 107 008
+#                                                             41x52: 18 240 / 56 576 / 84 480      40x16: 6 720 / 16 640 / 16 896
+#   x 10:  40x64: 220 800 / 698 880 / 1 070 080 (> 2^20)      41x52: 182 400 / 565 760 / 844 800   40x16: all below
+#   x 32:  40x64: 706 560 / 2 236 416 / 3 424 256             41x52: 583 680 / 1 810 432 / 2 703 360
+#          40x16: 215 040 / 532 480 / 540 672 (all below)
+# bf16 / fp16 at n = 32: block 1 is fp32 in every mode (count as above); blocks 2 and 3 store their pooled activation in 16 bits at
+# these widths (test_gpu_mode_matrix.py states the width rule), which the one-launch kernel does not serve.
+_SHAPE_ROWS = (
+    (Cell("fp32", "regression", True, "train", 10, (40, 64)), (2, 1, 0)),
+    (Cell("fp32", "classifier", False, "eval", 32, (40, 64)), (0, 0, 3)),
+    (Cell("fp32", "regression", False, "train", 32, (40, 64)), (1, 2, 0)),
+    (Cell("bf16", "regression", True, "train", 32, (40, 64)), (1, 2, 0)),
+    (Cell("fp16", "classifier", False, "eval", 32, (40, 64)), (0, 0, 3)),
+    (Cell("fp32", "regression", True, "train", 10, (64, 40)), (2, 1, 0)),
+    (Cell("fp32", "classifier", False, "eval", 32, (64, 40)), (0, 0, 3)),
+    (Cell("fp32", "regression", False, "train", 32, (64, 40)), (1, 2, 0)),
+    (Cell("bf16", "regression", True, "train", 32, (64, 40)), (1, 2, 0)),
+    (Cell("fp16", "classifier", False, "eval", 32, (64, 40)), (0, 0, 3)),
+    (Cell("fp32", "regression", True, "train", 10, (41, 52)), (3, 0, 0)),
+    (Cell("fp32", "classifier", False, "eval", 32, (41, 52)), (0, 0, 3)),
+    (Cell("fp32", "regression", False, "train", 32, (41, 52)), (1, 2, 0)),
+    (Cell("bf16", "regression", True, "train", 32, (41, 52)), (1, 2, 0)),
+    (Cell("fp16", "classifier", False, "eval", 32, (41, 52)), (0, 0, 3)),
+    (Cell("fp32", "regression", True, "train", 10, (40, 16)), (3, 0, 0)),
+    (Cell("fp32", "classifier", False, "eval", 32, (40, 16)), (0, 0, 3)),
+    (Cell("fp32", "regression", False, "train", 32, (40, 16)), (3, 0, 0)),
+    (Cell("bf16", "regression", True, "train", 32, (40, 16)), (1, 2, 0)),
+    (Cell("fp16", "classifier", False, "eval", 32, (40, 16)), (0, 0, 3)),
+)
+SHAPE_CELLS = tuple(c for c, _ in _SHAPE_ROWS)
+SHAPE_LAUNCHES = dict(_SHAPE_ROWS)
+
 
 def cell_id(c):
-    return f"{c.precision}-{c.head}-{'audio' if c.audio else 'noaudio'}-{c.mode}-n{c.n}"
+    shape = "" if c.hw == HW else f"-{c.hw[0]}x{c.hw[1]}"
+    return f"{c.precision}-{c.head}-{'audio' if c.audio else 'noaudio'}-{c.mode}-n{c.n}{shape}"
 
 
 def is_fp32(c):
@@ -103,12 +157,18 @@ def converged_stats(p, aud, vis, audio, head, seed=2025):
     return b
 
 
+def fixture(head, audio, mode, n, hw=HW):
+    """everything a cell starts from, at frames of hw = (H, W), as CPU tensors that nobody modifies (callers clone what a step updates
+    in place)"""
+    return _fixture(head, audio, mode, n, tuple(hw))
+
+
 @functools.lru_cache(maxsize=None)
-def fixture(head, audio, mode, n):
-    """everything a cell starts from, as CPU tensors that nobody modifies (callers clone what a step updates in place)"""
-    params = eval_ref.classifier_params(H, audio) if head == "classifier" else synth.make_params(H, H, 30, audio)
+def _fixture(head, audio, mode, n, hw):
+    h, w = hw
+    params = eval_ref.classifier_params(h, audio, w=w) if head == "classifier" else synth.make_params(h, w, 30, audio)
     fx = {"p": {k: torch.from_numpy(v.copy()) for k, v in params.items()},
-          "vis": torch.from_numpy(synth.make_visual(n, H, H)),
+          "vis": torch.from_numpy(synth.make_visual(n, h, w)),
           "aud": torch.from_numpy(synth.make_audio(n)) if audio else None,
           "lab": torch.from_numpy(synth.make_labels(n, seed=LABEL_SEED))}
     if mode == "train":
@@ -121,7 +181,7 @@ def fixture(head, audio, mode, n):
 
 
 def fixture_of(c):
-    return fixture(c.head, c.audio, c.mode, c.n)
+    return fixture(c.head, c.audio, c.mode, c.n, c.hw)
 
 
 def loss_fn(c):
@@ -293,7 +353,9 @@ def compare(c, fx, dev, log=print):
 # ---- the device ----------------------------------------------------------------------------------------------------------------------
 def run_device(c, fx, monkeypatch):
     """one train_step of the cell on the GPU. Returns the dict compare() reads; asserts what only the device can answer: the kernels the
-    mode selects ran (non-vacuity), eval mode moved no counter, fp16 overflowed nowhere."""
+    mode selects ran (non-vacuity), eval mode moved no counter, fp16 overflowed nowhere. Two entries are for the caller's own non-vacuity
+    assertions and are not read by compare(): "launches" = calls of (pool_bn_fwd_small, pool_bnstats_fwd, pool_bn_eval_fwd), "saved" =
+    (shape, dtype) of the pooled activations and 16-bit operands the context holds."""
     from cvml_goalnet_amd import AVM
     from test_gpu_eval import Counter
     train, half = c.mode == "train", not is_fp32(c)
@@ -308,6 +370,7 @@ def run_device(c, fx, monkeypatch):
         m.eval()
     m.keep_ctx = True
     pool_eval, pool_stats = Counter(monkeypatch, "pool_bn_eval_fwd"), Counter(monkeypatch, "pool_bnstats_fwd")
+    pool_small = Counter(monkeypatch, "pool_bn_fwd_small")
     drop0 = m._drop_step
     ctr0 = None if m._state is None else m._state.tolist()
     loss, pred = m.train_step(None if fx["aud"] is None else fx["aud"].to(DEV), fx["vis"].to(DEV), fx["lab"].to(DEV), lr=LR)
@@ -324,11 +387,11 @@ def run_device(c, fx, monkeypatch):
     if c.precision == "fp16":
         assert m._guard.tolist() == [0, 0], "the automatic loss scale overflowed"
     if not train:
-        assert pool_eval.calls == 3 and pool_stats.calls == 0, (pool_eval.calls, pool_stats.calls)
+        assert pool_eval.calls == 3 and pool_stats.calls == 0 and pool_small.calls == 0, (pool_eval.calls, pool_stats.calls, pool_small.calls)
         assert m._drop_step == drop0, "the dropout counter moved under eval()"
         assert int(m._state[1]) == (0 if ctr0 is None else ctr0[1]), "the device's dropout counter moved under eval()"
     else:
-        assert pool_eval.calls == 0
+        assert pool_eval.calls == 0 and pool_small.calls + pool_stats.calls == 3, (pool_small.calls, pool_stats.calls)
     assert pred.shape == ((n, eval_ref.CLS_C) if c.head == "classifier" else (n,))
     assert m.last_logit.shape == ((n, eval_ref.CLS_C) if c.head == "classifier" else (n,)), "last_logit is (n, C) under the classifier head"
     gates = _gates_first(ctx, n)
@@ -337,6 +400,8 @@ def run_device(c, fx, monkeypatch):
     dev = {"loss": loss.item(), "pred": pred.cpu(), "logit": m.last_logit.cpu().reshape(n, -1), "taps": _taps_first(ctx, n), "gates": gates,
            "grads": {k: m.grad_of(k).cpu() for k in fx["p"]}, "params": {k: sd1[k].cpu() for k in fx["p"]},
            "bufs": {k: sd1[k].cpu() for k in fx["b"]},
-           "classes": m.predict_classes(pred).cpu() if c.head == "classifier" else None}
+           "classes": m.predict_classes(pred).cpu() if c.head == "classifier" else None,
+           "launches": (pool_small.calls, pool_stats.calls, pool_eval.calls),
+           "saved": {k: (tuple(ctx[k].shape), ctx[k].dtype) for k in ("p1", "p2", "p3", "xh1", "xh2", "xh3") if ctx.get(k) is not None}}
     del ctx
     return dev

@@ -266,11 +266,12 @@ def test_float64_leaf_gets_a_float64_gradient():
 
 
 # ---- the other modes: one cell each ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cell", IC.CELLS, ids=cell_id)
+@pytest.mark.parametrize("cell", IC.CELLS + IC.SHAPE_CELLS, ids=cell_id)
 def test_input_gradients_of_the_other_modes(cell):
     fx = fixture_of(cell)
     w = IC.weights_of(cell)
     dev, m = IC.run_device(cell, fx, w)
+    assert dev["d_vis"].shape == (cell.n, 3, *cell.hw)
     IC.compare(cell, fx, dev, w)
     # the autograd surface of the same cell gives the same bits (fp16: the loss scale divided back out on both paths)
     m2 = IC.make_model(cell, fx)

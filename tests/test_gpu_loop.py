@@ -22,8 +22,9 @@ DEV = "cuda:0"
 LR = 1e-3
 
 
-def load_model(h, audio, precision="fp32", head="regression"):
-    params = eval_ref.classifier_params(h, audio) if head == "classifier" else synth.make_params(h, h, 30, audio)
+def load_model(h, audio, precision="fp32", head="regression", w=None):
+    w = h if w is None else w
+    params = eval_ref.classifier_params(h, audio, w=w) if head == "classifier" else synth.make_params(h, w, 30, audio)
     m = AVM(audio_included=audio, device=DEV, precision=precision, seed=synth.BASE_SEED, head=head)
     sd = {k: torch.from_numpy(v) for k, v in params.items()}
     sd.update(avm_ref.init_buffers())
@@ -92,8 +93,8 @@ def test_device_counter_kernels_match_their_host_scalar_twins():
     assert torch.equal(pc, pd)
 
 
-def _video(n, h, audio, salt):
-    vis = torch.from_numpy(synth.make_visual(n, h, h, seed=synth.BASE_SEED + salt))
+def _video(n, h, audio, salt, w=None):
+    vis = torch.from_numpy(synth.make_visual(n, h, h if w is None else w, seed=synth.BASE_SEED + salt))
     aud = torch.from_numpy(synth.make_audio(n, seed=synth.BASE_SEED + salt)) if audio else [None] * n
     lab = torch.from_numpy(synth.make_labels(n, seed=synth.BASE_SEED + salt))
     return aud, vis, lab
@@ -120,10 +121,25 @@ def _loop_counts(frames, sb):
     # sub-batches of 20 (> 16 rows): the captured graph holds the 16-bit linear5 / p3 / y3 kernels and the shadowed Adam
     pytest.param(True, "bf16", "regression", 20, id="True-bf16-sb20"), pytest.param(True, "fp16", "regression", 20, id="True-fp16-sb20")])
 def test_graph_loop_equals_eager_train_steps_bit_for_bit(audio, precision, head, sb):
-    h = 40
-    frames = (47, 33)                                                # sb = 10: 4x10 + 7, then 3x10 + 3; sb = 20: 2x20 + 7, then 20 + 13
-    videos = [_video(frames[0], h, audio, 1), _video(frames[1], h, audio, 2)]
-    eager, graphed = load_model(h, audio, precision, head), load_model(h, audio, precision, head)
+    # sb = 10: 4x10 + 7, then 3x10 + 3: sizes 10, 7, 3 ran eagerly once each, 6 replays; sb = 20: 2x20 + 7, then 20 + 13
+    _graph_loop_vs_eager(audio, precision, head, sb, (40, 40), (47, 33), {10: (3, 6), 20: (3, 2)}[sb], [sb])
+
+
+def test_graph_loop_equals_eager_train_steps_bit_for_bit_on_non_square_frames():
+    """two videos of 23 frames, 64 high and 40 wide: the staging tables are (cap, 3, 64, 40), and both the 10-row and the 3-row step are
+    captured (each size runs eagerly once, is captured at its second occurrence and replayed from then on) — on a square frame a table
+    or a gathered sub-batch laid out (W, H) holds the same bytes"""
+    tr = _graph_loop_vs_eager(True, "fp32", "regression", 10, (64, 40), (23, 23), (2, 4), [3, 10])
+    assert tr._key == ((64, 40), 30) and tr._vid.shape[1:] == (3, 64, 40)
+
+
+def _graph_loop_vs_eager(audio, precision, head, sb, hw, frames, counts, captured):
+    """VideoTrainer against the eager sequence of train_step calls on videos of `frames` frames of hw = (H, W): losses, predictions,
+    the state dict, the counters and the Adam moments bit for bit; `counts` = the (eager steps, replays) the caller worked out by
+    hand, `captured` = the sub-batch sizes that end up with a graph"""
+    h, w = hw
+    videos = [_video(f, h, audio, 1 + i, w=w) for i, f in enumerate(frames)]
+    eager, graphed = load_model(h, audio, precision, head, w=w), load_model(h, audio, precision, head, w=w)
     tr = VideoTrainer(graphed, subbatch_size=sb, lr=LR)
     for aud, vis, lab in videos:
         # eager: the reference's loop, main.py:177-196, on GPU tensors
@@ -137,11 +153,11 @@ def test_graph_loop_equals_eager_train_steps_bit_for_bit(audio, precision, head,
         torch.cuda.synchronize()
         assert torch.equal(losses, torch.cat(e_loss))
         assert torch.equal(preds, torch.cat(e_pred))
-    want_eager, want_replays = _loop_counts(frames, sb)               # sb = 10: sizes 10, 7, 3 ran eagerly once each, 6 replays
+    want_eager, want_replays = _loop_counts(frames, sb)
     steps = want_eager + want_replays
-    assert (want_eager, want_replays) == {10: (3, 6), 20: (3, 2)}[sb]
+    assert (want_eager, want_replays) == counts
     assert tr.replays == want_replays and tr.eager_steps == want_eager, (tr.replays, tr.eager_steps)
-    assert sorted(k[0] for k in tr._graphs) == [sb], "the full-size sub-batch is the one captured graph"
+    assert sorted(k[0] for k in tr._graphs) == captured, "the sub-batch sizes that occurred at least twice are the captured graphs"
     assert any(tr._uses_w5b.values()) == (sb > 16 and precision != "fp32"), "a graph of > 16 rows of a 16-bit mode reads the 16-bit weights"
     sd_e, sd_g = eager.state_dict(), graphed.state_dict()
     for k in sd_e:
@@ -150,6 +166,7 @@ def test_graph_loop_equals_eager_train_steps_bit_for_bit(audio, precision, head,
     assert torch.equal(graphed._adam_m, eager._adam_m) and torch.equal(graphed._adam_v, eager._adam_v)
     if precision == "fp16":
         assert graphed._guard.tolist() == [0, 0] and eager._guard.tolist() == [0, 0]
+    return tr
 
 
 @pytest.mark.parametrize("precision", ["bf16", "fp16"])

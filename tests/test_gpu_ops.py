@@ -462,6 +462,8 @@ def test_to_bf16_padded_layout_exact():
     (16, 11, 11, 512, 256, False, False), (2, 13, 13, 256, 64, False, False), (9, 40, 36, 64, 320, True, True),
     (1, 7, 5, 64, 256, True, True), (3, 7, 7, 64, 260, False, False),      # 35 / 147 pixels: the last quad of rows is only partly valid
     (40, 26, 22, 256, 64, False, False), (3, 9, 7, 64, 32, True, True),    # <= 64 output channels: the 128 x 64 tile (tile "128")
+    # frames of fewer than 64 pixels: a tile of 128 output pixels crosses more than two frames (conv3 of a 40 x 16 frame; 3 x 3 frames)
+    (32, 11, 3, 256, 512, True, True), (30, 3, 3, 64, 32, False, False),
 ])
 def test_conv3x3_fwd_bf16_padded_input(n, h, w, cin, cout, bias, relu, tile, monkeypatch):
     monkeypatch.setenv("GOALNET_BF16_TILE", tile)         # read by the entry point at call time; unset = chosen by size

@@ -156,6 +156,23 @@ def test_the_mode_comparison_passes_the_oracle_and_catches_a_wrong_device(index)
         IC.compare(c, fx, IC.oracle_device(c, fx, w, vis=fx["vis"].roll(1, 0)), w, log=lambda *_: None)
 
 
+@pytest.mark.parametrize("index", [0, 1], ids=["fp32-41x52", "bf16-64x40"])
+def test_the_mode_comparison_on_non_square_frames_passes_the_oracle_and_catches_a_wrong_device(index):
+    """the two cells on frames with H != W: the oracle passes; frames in another order fail, and so does a device that ran on frames
+    mirrored along W (its d_visual has the right shape and the right size everywhere, on the wrong pixels)"""
+    import _inputgrad_case as IC
+    c = IC.SHAPE_CELLS[index]
+    fx = IC.fixture_of(c)
+    w = IC.weights_of(c)
+    assert c.hw[0] != c.hw[1] and fx["vis"].shape == (c.n, 3, *c.hw)
+    dev = IC.oracle_device(c, fx, w)
+    assert dev["d_vis"].shape == (c.n, 3, *c.hw)
+    IC.compare(c, fx, dev, w)
+    for vis in (fx["vis"].roll(1, 0), fx["vis"].flip(3)):
+        with pytest.raises(AssertionError):
+            IC.compare(c, fx, IC.oracle_device(c, fx, w, vis=vis), w, log=lambda *_: None)
+
+
 def test_python_side_errors_come_before_any_device_work(monkeypatch):
     from cvml_goalnet_amd import AVM, GoalnetError
     monkeypatch.setattr(torch.cuda, "is_available", lambda: False)

@@ -8,7 +8,10 @@
     input swapped — a condition on the inputs and statistics (a cell whose output hardly depends on the frame could not see a row mix-up
     on the device either), never a measurement of the device;
   * DRY RUN of the runner's comparison: compare() accepts the oracle standing in for the device, and turns red when that stand-in ran
-    on swapped frames, or in train mode for an eval cell."""
+    on swapped frames, or in train mode for an eval cell;
+  * FRAMES WITH H != W (SHAPE_CELLS): the hand-written geometry table is the model's, compare() accepts the oracle on every cell (which
+    also settles the conditions that depend on the oracle alone: CLASS_GAP on every row, judge()), and the fp32 train cell of every
+    shape turns red on a stand-in that mixed H and W up."""
 import itertools
 
 import pytest
@@ -16,14 +19,14 @@ import torch
 
 import eval_ref
 from _golden import Golden
-from _mode_case import (CELLS, CLASS_GAP, GUARD_GRADS, TOL16, Cell, cell_id, compare, fixture_of, grad_verdict, is_fp32, oracle_as_device,
-                        oracle_grads)
+from _mode_case import (CELLS, CLASS_GAP, GUARD_GRADS, SHAPE_CELLS, SHAPE_GEOMETRY, SHAPE_LAUNCHES, TOL16, Cell, cell_id, compare,
+                        fixture_of, grad_verdict, is_fp32, oracle_as_device, oracle_grads)
 from cvml_goalnet_amd import synth
 from oracle import avm_ref
 from test_eval_golden import EVAL_CASES_SMALL, golden_buffers, head_of
 
 LEVELS = {"precision": ("fp32", "bf16", "fp16"), "head": ("regression", "classifier"), "audio": (True, False),
-          "mode": ("train", "eval"), "n": (10, 32)}
+          "mode": ("train", "eval"), "n": (10, 32), "hw": ((40, 40),)}
 
 
 def test_committed_cells_cover_every_three_way_combination():
@@ -187,3 +190,53 @@ def test_comparison_rejects_swapped_gradients_alone():
     dev["grads"].update({k: oracle_grads(cell, fx, vis=_swapped(fx["vis"]))[0][k] for k in GUARD_GRADS})
     with pytest.raises(AssertionError, match="gradient relative L2"):
         compare(cell, fx, dev, log=_quiet)
+
+
+# ---- frames with H != W -------------------------------------------------------------------------------------------------------------
+def test_shape_cells_are_the_five_cells_on_four_frames_and_keep_the_committed_ids():
+    from cvml_goalnet_amd import AVM
+    assert [cell_id(c) for c in CELLS[:2]] == ["bf16-classifier-noaudio-eval-n32", "bf16-classifier-noaudio-train-n10"]
+    assert cell_id(SHAPE_CELLS[0]) == "fp32-regression-audio-train-n10-40x64"
+    assert len(SHAPE_CELLS) == 20 == len(set(SHAPE_CELLS)) == len(SHAPE_LAUNCHES) and not set(SHAPE_CELLS) & set(CELLS)
+    five = {c[:5] for c in SHAPE_CELLS}
+    assert five == {("fp32", "regression", True, "train", 10), ("fp32", "classifier", False, "eval", 32),
+                    ("fp32", "regression", False, "train", 32), ("bf16", "regression", True, "train", 32),
+                    ("fp16", "classifier", False, "eval", 32)}
+    assert {c.hw for c in SHAPE_CELLS} == set(SHAPE_GEOMETRY) == {(40, 64), (64, 40), (41, 52), (40, 16)}
+    assert all(sum(1 for c in SHAPE_CELLS if c.hw == hw) == 5 for hw in SHAPE_GEOMETRY)
+    for hw, table in SHAPE_GEOMETRY.items():
+        assert hw[0] != hw[1] and AVM._sizes(*hw) == table, hw
+    for c, launches in SHAPE_LAUNCHES.items():
+        assert sum(launches) == 3 and (launches[2] == 3) == (c.mode == "eval"), c
+
+
+@pytest.mark.parametrize("cell", SHAPE_CELLS, ids=cell_id)
+def test_comparison_accepts_the_oracle_on_non_square_frames(cell):
+    """also what depends on the oracle alone at these shapes: no row of an fp32 classifier cell inside the class band (compare() asserts
+    CLASS_GAP on every row), every decision the oracle makes judged its own"""
+    fx = fixture_of(cell)
+    assert fx["vis"].shape == (cell.n, 3, *cell.hw)
+    hp3, wp3 = SHAPE_GEOMETRY[cell.hw][3]
+    assert fx["p"]["visbl.linear5.weight"].shape == (512, 512 * hp3 * wp3)
+    figures = compare(cell, fx, oracle_as_device(cell, fx), log=print)
+    assert figures["disagree"] == 0
+
+
+@pytest.mark.parametrize("cell", [c for c in SHAPE_CELLS if (c.precision, c.mode, c.n) == ("fp32", "train", 10)], ids=cell_id)
+def test_comparison_rejects_a_device_that_mixed_height_and_width_up(cell):
+    """the wrong device is the oracle with linear5.weight's columns re-ordered as if p3 were flattened (C, W, H) — what a (512, C, HW)
+    view built from (wp3, hp3) would read. Measured logit errors: 1.2e-2 at 64 x 40, 2.0e-2 at 41 x 52, against 2e-5. At 40 x 16 p3 is
+    one pixel wide and that re-ordering is the identity: there the wrong device ran on frames mirrored along W, which block 2's and
+    block 3's geometry (5 and 3 pixels wide) must tell from the cell's own."""
+    fx = fixture_of(cell)
+    hp3, wp3 = SHAPE_GEOMETRY[cell.hw][3]
+    if wp3 > 1:
+        w5 = fx["p"]["visbl.linear5.weight"]
+        wrong = w5.view(512, 512, hp3, wp3).transpose(2, 3).reshape(512, -1)
+        assert not torch.equal(wrong, w5)
+        dev = oracle_as_device(cell, dict(fx, p=dict(fx["p"], **{"visbl.linear5.weight": wrong})))
+        with pytest.raises(AssertionError, match="logits .* from the oracle's"):
+            compare(cell, fx, dev, log=_quiet)
+    else:
+        with pytest.raises(AssertionError):
+            compare(cell, fx, oracle_as_device(cell, fx, vis=fx["vis"].flip(3)), log=_quiet)

@@ -184,6 +184,39 @@ def trainable_ranges(specs, frozen, skipped):
     return out
 
 
+EPI_FUSE_MIN_ROWS = 256        # frames from which linear5's weight gradient carries Adam in its epilogue (the size of _large_overlap)
+EPI_FUSE_SKINNY_ROWS = 16      # up to here linear5 runs on the weight-streaming kernels, which have no such epilogue
+
+
+def epi_fuse_pieces(env):
+    """GOALNET_F32_EPI_FUSE (read per call) -> the set of fused epilogue pieces that may run: unset or "1" all of them, "0" none
+    (the launches as before), otherwise the pieces named by letter ("a": linear5 dW + Adam). Pure: the host tests call it."""
+    if env is None or env in ("", "1"):
+        return frozenset("a")
+    if env == "0":
+        return frozenset()
+    return frozenset(ch for ch in env.lower() if ch in "a")
+
+
+def epi_fuse_dw_adam(n, *, plain, synced, precision, train_w5, shadowed, inspected, forced, pieces):
+    """linear5's weight gradient with the Adam update of linear5.weight in its epilogue (ops.linear_bwd_dw_adam) for this
+    train_step? Only where the early Adam would be legal — every tensor trains under the global step count (`plain`), no gradient
+    exchange, the fp32 engine (no overflow guard, no 16-bit copy of the weight to refresh: `shadowed`) — linear5.weight trains, and
+    the step is large: `forced` (model.epi_fuse) True drops the size rule down to the 128 x 128 tile's smallest step, False and a
+    GOALNET_F32_EPI_FUSE without "a" switch the piece off. A step that is kept for inspection (`inspected`: model.keep_ctx) writes
+    every gradient unless the piece is forced: the fused launch leaves linear5.weight's gradient slot alone. Pure: the host tests
+    call it."""
+    if forced is False or "a" not in pieces:
+        return False
+    if inspected and forced is not True:
+        return False
+    if not (plain and not synced and precision == "fp32" and train_w5 and not shadowed):
+        return False
+    if n <= EPI_FUSE_SKINNY_ROWS:
+        return False
+    return forced is True or n >= EPI_FUSE_MIN_ROWS
+
+
 class AVM(_LazyFlags, nn.Module):
     def __init__(self, audio_included, device=None, seed: Optional[int] = None, precision: str = "fp32", head: str = "regression",
                  num_classes: int = 5):
@@ -282,6 +315,9 @@ class AVM(_LazyFlags, nn.Module):
         self.small_bn = env("GOALNET_SMALL_BN", "1") != "0"           # _small_bn
         self.force_bf5 = env("GOALNET_FORCE_BF5") == "1"              # _bf5
         self.overlap_pair = env("GOALNET_OVERLAP_PAIR", "1") != "0"   # _pair
+        # fp32 GEMM epilogue fusion (epi_fuse_dw_adam above): None = the size rule, True = also below it (tests), False = never
+        self.epi_fuse = None
+        self.epi_fused_dw = 0          # train_steps so far whose linear5 weight gradient ran with Adam in its epilogue
         self.keep_ctx = False          # tests: keep the last train_step's / input_gradients' saved tensors in last_ctx
         self.last_ctx = None
         self.last_used_w5b = False
@@ -1061,7 +1097,8 @@ class AVM(_LazyFlags, nn.Module):
             wgrad()                                  # behind the data gradient: runs under the next block's BatchNorm / pool passes
         return dx
 
-    def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None, inputs=None, params=True, reduce=0, frozen=None):
+    def backward_device(self, ctx, dout, on_bucket=None, after_linear5=None, inputs=None, params=True, reduce=0, frozen=None,
+                        fused_w5=None):
         """dout (N,) GPU. Fills the gradient arena (the slot of every TRAINABLE tensor is overwritten). `inputs` = (audio?, visual?): also
         follow the data-gradient chain into the inputs and return (d_audio (N,30,B) | None, d_visual (N,3,H,W) | None) — `reduce`=1:
         d_visual is max_ci |.|, (N,H,W).
@@ -1074,6 +1111,9 @@ class AVM(_LazyFlags, nn.Module):
         bucket k of ddp.bucket_slices() is complete (0: fusion+audbl+linear5.bias, 1: linear5.weight, 2: rest).
         `after_linear5(fork)`: called once linear5's weight gradient (side stream) and data gradient (main stream) are both
         enqueued — from there on nothing reads linear5.weight or its 16-bit copy again in this step (train_step's early Adam).
+        `fused_w5(dz5, p3, scale, shift)` (fp32 engine, train_step's rule epi_fuse_dw_adam): called on the main stream INSTEAD of
+        linear5's weight gradient launch and AFTER its data gradient, the last reader of the old weights; it computes the gradient and
+        applies it in one launch, and the gradient slot of visbl.linear5.weight is not written.
         Every refusal is raised before the first launch or allocation, as on the C side: a refused call leaves the gradient arena and
         both streams as they were."""
         need_aud, need_vis = inputs if inputs is not None else (False, False)
@@ -1237,11 +1277,14 @@ class AVM(_LazyFlags, nn.Module):
                 if need_b3:
                     ops.linear_bwd_dx_split(self._parts, dz5s, ctx["w5s"], dbn3.view(n, k5), n, k5, 512, oscale=self._osc(adz, ctx["w5s_amax"]))
             else:
-                if train_w5:
+                fuse5 = fused_w5 is not None and train_w5
+                if train_w5 and not fuse5:
                     fork.run(lambda: ops.linear_bwd_dw(dz5, p3f, G("visbl.linear5.weight"), scale=st3[2], shift=st3[3], bnC=512), dz)
                 bucket_done(1)
                 if need_b3:
                     ops.linear_bwd_dx(dz5, P("visbl.linear5.weight"), dbn3.view(n, k5), mult=None)
+                if fuse5:
+                    fused_w5(dz5, p3f, st3[2], st3[3])      # updates linear5.weight in place: behind its last reader of the step
             linear5_done()
         else:
             bucket_done(1)
@@ -1376,7 +1419,10 @@ class AVM(_LazyFlags, nn.Module):
         """main.py:187-193 on GPU tensors. Returns (loss (1,), pred (N,)) as GPU tensors, no host sync.
         `_loop_tick`: (frames, sub-batches) the caller's loop counters advance by (loop.VideoTrainer); `_scatter(loss, pred)` -> row-copy
         segments (ops.rows_copy_batch form, cursors as they stand BEFORE the tick) that the step's last launch writes before it advances
-        the counters (the per-video predictions / losses arrays of loop.VideoTrainer)."""
+        the counters (the per-video predictions / losses arrays of loop.VideoTrainer).
+        fp32 steps of >= 256 frames in which every tensor trains and no gradient is exchanged (epi_fuse_dw_adam) update
+        visbl.linear5.weight inside its weight-gradient GEMM: that tensor's slot of the gradient arena is then NOT written, and
+        grad_of("visbl.linear5.weight") returns whatever an earlier backward left there. keep_ctx = True or epi_fuse = False keep it."""
         frozen = self._frozen_names()                   # requires_grad=False: no gradient, no update, no step counted (DESIGN.md §4.11)
         self._check_freeze(frozen)
         plain = self._plain_step(frozen)                # every tensor trains under the global step count: today's launches
@@ -1414,6 +1460,14 @@ class AVM(_LazyFlags, nn.Module):
         # side stream, i.e. 36 GB of HBM traffic under the MFMA-bound convolution gradients that follow instead of after them
         # (with frozen or re-thawed tensors the update is ONE launch over the trainable ranges after backward: no early pass)
         early = plain and sync is None and self.precision != "fp16" and self._large_overlap(n) and self._fork_ok(n)
+        # The fp32 engine at large sizes runs serial (no fork), so that pass would be fully exposed: there the update of linear5.weight
+        # runs in the epilogue of its weight-gradient GEMM instead (ops.linear_bwd_dw_adam, same bits), after the data gradient. The
+        # gradient slot of visbl.linear5.weight in the arena is then NOT written: grad_of() of that tensor holds what an earlier,
+        # unfused backward left there. keep_ctx = True (a step kept for inspection) or epi_fuse = False keep the gradient.
+        fuse5 = epi_fuse_dw_adam(n, plain=plain, synced=sync is not None, precision=self.precision,
+                                 train_w5="visbl.linear5.weight" not in frozen, shadowed=self._w5b is not None, inspected=self.keep_ctx,
+                                 forced=self.epi_fuse, pieces=epi_fuse_pieces(os.environ.get("GOALNET_F32_EPI_FUSE")))
+        early = early and not fuse5
         # (small steps: the same update as a background pass on a third stream was measured slower at every width)
         done_early = []
 
@@ -1426,8 +1480,17 @@ class AVM(_LazyFlags, nn.Module):
                 self._adam_piece(lo, hi, lo, lr, betas, eps, 1.0 / lscale)
             fork.run(piece)
             done_early.append((lo, hi))
+
+        def dw_adam(dz5, p3f, scale, shift):
+            s5 = self.spec("visbl.linear5.weight")
+            lo, hi = s5.offset, s5.offset + s5.numel
+            self._adam_state()                       # the first step allocates the moments
+            ops.linear_bwd_dw_adam(dz5, p3f, self._arena[lo:hi], self._adam_m[lo:hi], self._adam_v[lo:hi], lr, betas[0], betas[1], eps,
+                                   self._state[0], scale=scale, shift=shift, bnC=512, grad_scale=1.0 / lscale, step_bias=1)
+            done_early.append((lo, hi))
+            self.epi_fused_dw += 1
         self.backward_device(ctx, dout, on_bucket=(lambda k: sync.on_bucket(self, k)) if sync is not None else None,
-                             after_linear5=early_adam if early else None, frozen=frozen)
+                             after_linear5=early_adam if early else None, frozen=frozen, fused_w5=dw_adam if fuse5 else None)
         scale = 1.0
         if sync is not None:
             scale = sync.finish(self)

@@ -21,6 +21,7 @@
 // MFMA steps; rows are padded to 36 floats, which makes those reads bank-conflict free.
 #include <stdlib.h>
 
+#include "adam.h"
 #include "gemm_common.h"
 #include "skinny.h"
 
@@ -679,6 +680,59 @@ __device__ __forceinline__ void store_acc_n64(const EpiP& ep, const f32x16 (&acc
     }
 }
 
+// The K loop of one output tile as a function: loaders, LDS staging and MFMAs for K-tiles [kt0, kt1) of tile (tm, tn) into the
+// wave's 2 x 2 accumulator tiles (128 x 128 tile, per-K-tile loaders). gemm_f32_epi_kernel runs it; gemm_f32_kernel keeps its own
+// inline copy of the same statements: calling this function from it changed the register allocation of every instantiation
+// (VGPRs and spills moved by 1-7), and those kernels are to compile as they did.
+template <class AL, class BL, int STAGES>
+__device__ __forceinline__ void gemm_mainloop(const typename AL::P& ap, const typename BL::P& bp, int tm, int tn, int kt0, int kt1,
+                                              int tid, f32x16 (&acc)[2][2]) {
+    static_assert(!AL::STRIP, "per-K-tile A loaders only");
+    AL al(ap, tm * BM, tid);
+    BL bl(bp, tn * BN, tid);
+
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    __shared__ __attribute__((aligned(16))) float lds[STAGES][2][OP_FLOATS];
+    float4 ra[4], rb[4];
+    if (kt0 < kt1) {
+        al.issue(kt0, ra);
+        bl.issue(kt0, rb);
+        al.finish(ra);
+        bl.finish(rb);
+        store_tile<AL::KC>(lds[0][0], ra, tid);
+        store_tile<BL::KC>(lds[0][1], rb, tid);
+    }
+    __syncthreads();
+    for (int kt = kt0; kt < kt1; ++kt) {
+        const int cur = STAGES == 1 ? 0 : (kt - kt0) & 1;
+        const bool more = kt + 1 < kt1;
+        if (more) {
+            // the buffer being filled was last read in iteration kt-1, which every wave left through the barrier
+            al.issue(kt + 1, ra);
+            bl.issue(kt + 1, rb);
+        }
+        compute_tile<AL::KC, BL::KC>(lds[cur][0], lds[cur][1], acc, wm, wn, r, h);
+        if constexpr (STAGES == 1) __syncthreads();      // one LDS stage: every wave has read it
+        if (more) {
+            al.finish(ra);
+            bl.finish(rb);
+            store_tile<AL::KC>(lds[STAGES == 1 ? 0 : cur ^ 1][0], ra, tid);
+            store_tile<BL::KC>(lds[STAGES == 1 ? 0 : cur ^ 1][1], rb, tid);
+        }
+        __syncthreads();
+    }
+}
+
 // ---- the kernel: 256 threads, every wave stages and computes, 2 blocks per CU ---------------------------------------
 // Measured ceilings on conv3 forward (scripts/bench_gemm.py, N = 128, 2.37 GHz): 147 TFLOP/s with no staging in the
 // loop, 135 with only the global loads or only the LDS writes, 127 with both. Two restructurings were built, found
@@ -789,6 +843,106 @@ __global__ __launch_bounds__(256, STAGES == 1 ? (N64 ? 4 : AL::ONE_STAGE_BLOCKS)
         const int nsp = (ktiles + ktiles_per_split - 1) / ktiles_per_split;
         fused_splitk_reduce<N64 ? 64 : BN>(ep, tm, tn, tm * tiles_n + tn, nsp, tid);
     }
+}
+
+// ---- epilogues that consume the accumulators instead of (only) storing them ------------------------------------------
+// gemm_f32_epi_kernel is gemm_f32_kernel's loop (gemm_mainloop) under an epilogue picked by a TEMPLATE parameter: a runtime
+// branch inside store_acc's unrolled loop once sent the accumulators to scratch (gemm_common.h, EpiP::oscale). It is a
+// kernel of its own, so the instantiations of gemm_f32_kernel keep their names (bench.py and the profiles name kernels by
+// them) and their code. No split-K, 128 x 128 tile.
+//
+// EPIK_ADAM (linear5's weight gradient): the tile's accumulators ARE the gradient of 128 x 128 elements of the weight, and
+// dw[j][k] (ld = K) is the arena layout, so p, m and v are addressed by the gradient's own index: load p / m / v, adam1,
+// store p / m / v. No gradient is written; the 5.1 GB round trip of dW through HBM and the stand-alone pass's launch go, and
+// the update's 30.8 GB move under an MFMA-bound kernel. With both operands row-contiguous a lane's fragments fn = 0, 1 are
+// the adjacent columns 2r, 2r + 1: 8-byte accesses, 256 B contiguous per row and half-wave.
+enum { EPIK_ADAM = 1 };
+
+struct AdamEpi {
+    float* p; float* m; float* v;
+    double lr, beta1, beta2;
+    float eps, gs;
+    const int64_t* step; int64_t step_bias;
+};
+
+__device__ __forceinline__ float wave_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+
+// rows = J, cols = K (a multiple of 4: a lane's column pair is inside or outside together), ld = K.
+__device__ __forceinline__ void adam_acc(const AdamEpi& ae, const AdamScalars& s, int rows, int cols, int64_t ld,
+                                         const f32x16 (&acc)[2][2], int tm, int tn, int wm, int wn, int r, int h) {
+    const int col = tn * GEMM_BN + wn * 64 + 2 * r;
+    const bool colok = col < cols;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm) {
+        const int row0 = tm * GEMM_BM + wm * 64 + fm + 8 * h;
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) {
+            // four rows at a time: 12 loads in flight, then the arithmetic, then the stores. Lanes outside the matrix load
+            // element 0 (a valid address) and store nothing: no branch around a load.
+            float2 pp[4], mm[4], vv[4];
+            int64_t idx[4];
+            bool ok[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = row0 + 2 * (q + 8 * eb);
+                ok[q] = colok && row < rows;
+                idx[q] = ok[q] ? (int64_t)row * ld + col : 0;
+                pp[q] = *reinterpret_cast<const float2*>(ae.p + idx[q]);
+                mm[q] = *reinterpret_cast<const float2*>(ae.m + idx[q]);
+                vv[q] = *reinterpret_cast<const float2*>(ae.v + idx[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * eb + q;
+                adam1(pp[q].x, acc[fm][0][e], mm[q].x, vv[q].x, s.b2, s.omb1, s.omb2, ae.eps, s.step_size, s.bc2_sqrt, ae.gs);
+                adam1(pp[q].y, acc[fm][1][e], mm[q].y, vv[q].y, s.b2, s.omb1, s.omb2, ae.eps, s.step_size, s.bc2_sqrt, ae.gs);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (ok[q]) {
+                    *reinterpret_cast<float2*>(ae.p + idx[q]) = pp[q];
+                    *reinterpret_cast<float2*>(ae.m + idx[q]) = mm[q];
+                    *reinterpret_cast<float2*>(ae.v + idx[q]) = vv[q];
+                }
+            }
+        }
+    }
+}
+
+template <class AL, class BL, int STAGES, int EPI>
+__global__ __launch_bounds__(256, STAGES == 1 ? AL::ONE_STAGE_BLOCKS : 2) void gemm_f32_epi_kernel(typename AL::P ap, typename BL::P bp, AdamEpi ae,
+                                                          int rows, int cols, int64_t ld, int tiles_m, int tiles_n, int m_fast, int ktiles) {
+    static_assert(EPI == EPIK_ADAM && !AL::KC && !BL::KC, "the Adam epilogue: both operands row-contiguous");
+    const int tid = threadIdx.x;
+    int tm, tn;
+    tile_of_block(tiles_m, tiles_n, m_fast, tm, tn);
+    // the step's scalars before the loop, while no accumulator is live (fp64 pow), kept in scalar registers through it
+    AdamScalars s = adam_scalars(ae.lr, ae.beta1, ae.beta2, *ae.step + ae.step_bias);
+    s.step_size = wave_uniform(s.step_size); s.bc2_sqrt = wave_uniform(s.bc2_sqrt);
+    s.b2 = wave_uniform(s.b2); s.omb1 = wave_uniform(s.omb1); s.omb2 = wave_uniform(s.omb2);
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc[2][2];
+    gemm_mainloop<AL, BL, STAGES>(ap, bp, tm, tn, 0, ktiles, tid, acc);
+    adam_acc(ae, s, rows, cols, ld, acc, tm, tn, wm, wn, r, h);
+}
+
+template <class AL, class BL, int EPI>
+int launch_gemm_epi(const char* name, const typename AL::P& ap, const typename BL::P& bp, const AdamEpi& ae, int64_t M, int64_t N,
+                    int64_t ld, int ktiles, int m_fast, hipStream_t st) {
+    const int64_t tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    GN_REQUIRE(tiles_m * tiles_n < (1ll << 31), GOALNET_E_SHAPE, "%s: too many tiles", name);
+    static const int force_stages = getenv("GOALNET_F32_STAGES") ? atoi(getenv("GOALNET_F32_STAGES")) : 0;      // as launch_gemm
+    const dim3 grid((unsigned)(tiles_m * tiles_n), 1, 1);
+    if (force_stages == 1 || (force_stages != 2 && AL::ONE_STAGE))
+        hipLaunchKernelGGL((gemm_f32_epi_kernel<AL, BL, 1, EPI>), grid, dim3(256), 0, st, ap, bp, ae, (int)M, (int)N, ld, (int)tiles_m,
+                           (int)tiles_n, m_fast, ktiles);
+    else
+        hipLaunchKernelGGL((gemm_f32_epi_kernel<AL, BL, 2, EPI>), grid, dim3(256), 0, st, ap, bp, ae, (int)M, (int)N, ld, (int)tiles_m,
+                           (int)tiles_n, m_fast, ktiles);
+    GN_LAUNCH_CHECK(name);
+    return 0;
 }
 
 // sums `nsplit` raw slabs (deterministic order) and applies the epilogue. cols % 4 == 0.
@@ -1233,6 +1387,36 @@ int goalnet_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t
     }
     MCLoader<false>::P bp{x, ldx, (int)K, M, nullptr, nullptr, 1};
     return launch_gemm<MCLoader<false>, MCLoader<false>>("linear_bwd_dw", ap, bp, ep, J, K, ktiles, 1, 1, st);
+}
+
+/* goalnet_linear_bwd_dw followed by goalnet_adam_step_dev on p / m / v [J][K] (1-based step count *step + step_bias), in one
+ * launch and with the same bits: the Adam update runs in the GEMM's epilogue on the accumulators, the gradient is never
+ * written (EPIK_ADAM). Served by the 128 x 128 tile only: M <= SKINNY_MAX_M is refused (the caller keeps the two launches). */
+int goalnet_linear_bwd_dw_adam(const float* dy, int64_t lddy, const float* x, int64_t ldx,
+                               const float* scale, const float* shift, int bnC,
+                               float* p, float* m, float* v, float* db, int M, int64_t K, int J,
+                               double lr, double beta1, double beta2, double eps, const int64_t* step, int64_t step_bias,
+                               float grad_scale, void* stream) {
+    GN_REQUIRE(dy && x && p && m && v && step, GOALNET_E_NULL, "linear_bwd_dw_adam: null pointer");
+    GN_REQUIRE((scale == nullptr) == (shift == nullptr), GOALNET_E_NULL, "linear_bwd_dw_adam: scale/shift must both be set or both NULL");
+    GN_REQUIRE(M > 0 && J > 0 && K > 0 && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dw_adam: bad dims");
+    GN_REQUIRE(J % 4 == 0 && K % 4 == 0, GOALNET_E_SHAPE, "linear_bwd_dw_adam: J and K must be multiples of 4");
+    GN_REQUIRE(!scale || (bnC > 0 && bnC % 4 == 0), GOALNET_E_SHAPE, "linear_bwd_dw_adam: bnC must be a positive multiple of 4");
+    GN_REQUIRE(M > SKINNY_MAX_M, GOALNET_E_SHAPE, "linear_bwd_dw_adam: M=%d is served by the weight-streaming kernels (M > %d here)", M, SKINNY_MAX_M);
+    GN_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(scale) && aligned16(shift) && lddy % 4 == 0 && ldx % 4 == 0,
+               GOALNET_E_ALIGN, "linear_bwd_dw_adam: pointers / leading dims must be 16-byte aligned");
+    GN_REQUIRE(aligned16(p) && aligned16(m) && aligned16(v), GOALNET_E_ALIGN, "linear_bwd_dw_adam: p, m and v must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (db) { const int rc = goalnet_colsum(dy, lddy, M, J, db, stream); if (rc) return rc; }
+    const int ktiles = (M + BK - 1) / BK;
+    MCLoader<false>::P ap{dy, lddy, J, M, nullptr, nullptr, 1};
+    const AdamEpi ae{p, m, v, lr, beta1, beta2, (float)eps, grad_scale, step, step_bias};
+    if (scale) {
+        MCLoader<true>::P bp{x, ldx, (int)K, M, scale, shift, bnC};
+        return launch_gemm_epi<MCLoader<false>, MCLoader<true>, EPIK_ADAM>("linear_bwd_dw_adam", ap, bp, ae, J, K, K, ktiles, 1, st);
+    }
+    MCLoader<false>::P bp{x, ldx, (int)K, M, nullptr, nullptr, 1};
+    return launch_gemm_epi<MCLoader<false>, MCLoader<false>, EPIK_ADAM>("linear_bwd_dw_adam", ap, bp, ae, J, K, K, ktiles, 1, st);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 // 57 % of the reference's step at its own sub-batch size.
 #include <hip/hip_bf16.h>
 
+#include "adam.h"
 #include "common.h"
 #include "mse.h"
 
@@ -390,17 +391,9 @@ __global__ __launch_bounds__(256) void mse_bcast_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam defaults, single-tensor operation order), one pass over the flat arena.
+// Adam (torch.optim.Adam defaults, single-tensor operation order), one pass over the flat arena. The per-element update
+// (adam1) and the step's scalars (adam_scalars) live in adam.h: the weight-gradient GEMM's epilogue runs the same code.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b2, float omb1, float omb2,
-                                      float eps, float step_size, float bc2_sqrt, float gs) {
-    g *= gs;
-    m = m + omb1 * (g - m);                    // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * b2 + (omb2 * g) * g;               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-    const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p - step_size * (m / denom);           // param.addcdiv_(exp_avg, denom, value = -step_size)
-}
-
 // four updated parameters as binary16 (f16 != 0) or bfloat16, packed for one 8-byte store into the 16-bit copy
 __device__ __forceinline__ uint2 pack4_16(const float4& pp, int f16) {
     if (f16) {
@@ -423,10 +416,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     const int64_t ti = step_dev ? *step_dev + step_host : step_host;               // device counter + bias, or the host count
     // precision = "fp16": goalnet_grad_finite_check stamped this step as overflowed -> the whole update is skipped
     if (bad_step && *bad_step == ti) return;
-    const double t = (double)ti;
-    const float step_size = (float)(lr / (1.0 - pow(beta1, t)));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
-    const float b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+    const AdamScalars sc = adam_scalars(lr, beta1, beta2, ti);
+    const float step_size = sc.step_size, bc2_sqrt = sc.bc2_sqrt, b2 = sc.b2, omb1 = sc.omb1, omb2 = sc.omb2;
     const int64_t n4 = n >> 2;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -470,10 +461,8 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p,
     int r = 0;
     while (r + 1 < nranges && (int)blockIdx.x >= rs.first_block[r + 1]) ++r;
     const int64_t lb = (int)blockIdx.x - rs.first_block[r], nb = rs.first_block[r + 1] - rs.first_block[r];
-    const double t = (double)(t1 - rs.skipped[r]);
-    const float step_size = (float)(lr / (1.0 - pow(beta1, t)));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, t));
-    const float b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+    const AdamScalars sc = adam_scalars(lr, beta1, beta2, t1 - rs.skipped[r]);
+    const float step_size = sc.step_size, bc2_sqrt = sc.bc2_sqrt, b2 = sc.b2, omb1 = sc.omb1, omb2 = sc.omb2;
     const int64_t begin = rs.begin[r], n = rs.count[r], b4 = begin >> 2, n4 = n >> 2;
     for (int64_t j = lb * blockDim.x + threadIdx.x; j < n4; j += nb * blockDim.x) {
         const int64_t i = b4 + j;                         // float4 index in the arena

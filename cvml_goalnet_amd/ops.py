@@ -657,6 +657,20 @@ def linear_bwd_dw(dy, x, dw, *, scale=None, shift=None, bnC=0, db=None):
     return dw
 
 
+def linear_bwd_dw_adam(dy, x, p, m, v, lr, beta1, beta2, eps, step, *, scale=None, shift=None, bnC=0, db=None, grad_scale=1.0, step_bias=0):
+    """linear_bwd_dw + adam_step_dev on p / m / v (laid out like dw, [J][K]) in one launch, same bits; the gradient is not written.
+    Rows above the weight-streaming kernels' limit only (M > 16): the C side refuses the rest."""
+    _chk(dy, x, p, m, v, scale, shift, db)
+    M, J = dy.shape
+    K = x.shape[1]
+    _req(p.numel() == J * K and m.numel() == J * K and v.numel() == J * K and x.shape[0] == M and (db is None or db.numel() == J),
+         "linear_bwd_dw_adam: argument check failed: p.numel() == m.numel() == v.numel() == J * K and x.shape[0] == M and (db is None or db.numel() == J)")
+    _req(p.is_contiguous() and m.is_contiguous() and v.is_contiguous(), "linear_bwd_dw_adam: p, m and v must be contiguous")
+    check(lib().goalnet_linear_bwd_dw_adam(dy.data_ptr(), _ld(dy), x.data_ptr(), _ld(x), _p(scale), _p(shift), bnC, p.data_ptr(), m.data_ptr(),
+                                           v.data_ptr(), _p(db), M, K, J, lr, beta1, beta2, eps, _ctr(step), int(step_bias), grad_scale, _s()),
+          "linear_bwd_dw_adam")
+
+
 def colsum(x, out):
     _chk(x, out)
     M, J = x.shape

@@ -292,6 +292,16 @@ int goalnet_linear_bwd_dx(const float* dy, int64_t lddy, const float* w, const f
 int goalnet_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t ldx,
                           const float* scale, const float* shift, int bnC,
                           float* dw, float* db, int M, int64_t K, int J, void* stream);
+/* goalnet_linear_bwd_dw followed by goalnet_adam_step_dev (step count *step + step_bias) on p / m / v [J][K], in ONE launch and
+ * with the same bits: the update runs in the GEMM's epilogue on the accumulators of each 128 x 128 tile of the gradient, which
+ * is never written (no dw argument). p, m, v: 16-byte aligned, J * K floats each, indexed like dw. M must be above the
+ * weight-streaming kernels' row count (M > 16): smaller steps are refused with GOALNET_E_SHAPE and keep the two launches.
+ * Every refusal happens before the first launch. */
+int goalnet_linear_bwd_dw_adam(const float* dy, int64_t lddy, const float* x, int64_t ldx,
+                               const float* scale, const float* shift, int bnC,
+                               float* p, float* m, float* v, float* db, int M, int64_t K, int J,
+                               double lr, double beta1, double beta2, double eps, const int64_t* step, int64_t step_bias,
+                               float grad_scale, void* stream);
 /* out[j] = sum_m x[m][j] (deterministic) — bias gradients */
 int goalnet_colsum(const float* x, int64_t ldx, int M, int J, float* out, void* stream);
 /* y = x * mult (elementwise over [M][J] with leading dims) */

@@ -168,6 +168,17 @@ PROTOTYPES = {
     "goalnet_rows_scatter": (c_int, [P, P, c_int64, c_int, P, P]),
 }
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_loss.h, the second public header: additions
+# that leave include/goalnet_hip.h, PROTOTYPES and ABI_VERSION as they are
+LOSS_PROTOTYPES = {
+    "goalnet_frame_loss_ws_bytes": (c_size_t, [c_int, c_int]),
+    "goalnet_frame_loss": (c_int, [c_int, c_double, P, P, P, c_int, P, P, P, c_size_t, P]),
+    "goalnet_mlp_fwd_loss": (c_int, [P, c_int64, c_int, P, P, P, P, P, P, P, P, P, P, P, c_int, c_double, P, c_int, P, P]),
+}
+# GOALNET_LOSS_* (include/goalnet_loss.h)
+LOSS_KINDS = {"mse_bcast": 0, "mse": 1, "l1": 2, "smooth_l1": 3, "rank": 4}
+FRAME_LOSS_MAX_N = 65536
+
 _lib = None
 
 
@@ -185,7 +196,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -836,10 +836,11 @@ class AVM(_LazyFlags, nn.Module):
         # the conv output is only an input of the pool: backward reads the ReLU mask off p (csrc/pool_bn.hip)
         return (*self._bn_block(y, n, hc, wc, cout, i, save, p16=p16), xh)
 
-    def forward_device(self, audio, visual, save: bool, *, fused_loss=None, caller_ticks: bool = False):
+    def forward_device(self, audio, visual, save: bool, *, fused_loss=None, caller_ticks: bool = False, fused_loss_kind=None):
         """audio (N,30,B) / None, visual (N,3,H,W): contiguous fp32 GPU tensors. Returns (out (N,), ctx); ctx is None unless `save`.
         train_step's two riders: `fused_loss` = (labels, loss, dout) — where the one-launch MLP runs, it evaluates the broadcast MSE too
-        (ctx["loss_done"] says whether it did); `caller_ticks`: the dropout draw counter is advanced by the caller, by ctx["drop_ticks"]."""
+        (ctx["loss_done"] says whether it did), or, with `fused_loss_kind` = (name, param, weights), that loss (ops.loss_spec);
+        `caller_ticks`: the dropout draw counter is advanced by the caller, by ctx["drop_ticks"]."""
         if visual.dim() != 4 or visual.shape[1] != 3:
             raise RuntimeError(f"visual_input must be (N,3,H,W), got {tuple(visual.shape)}")
         n, _, h, w = visual.shape
@@ -942,8 +943,11 @@ class AVM(_LazyFlags, nn.Module):
                 ms.append(torch.empty(n, width, dtype=F32, device=dev) if save else None)
             logit = torch.empty(n, dtype=F32, device=dev)
             out = torch.empty(n, dtype=F32, device=dev)
+            lkw = {}
+            if fused_loss is not None and fused_loss_kind is not None:
+                lkw = dict(loss_kind=fused_loss_kind[0], loss_param=fused_loss_kind[1], weights=fused_loss_kind[2])
             ops.mlp_fwd(cat, [P(f"fusion.{k}.weight") for k in keys], [P(f"fusion.{k}.bias") for k in keys], masks[1:5],
-                        hs[1:], ms[1:], logit, out, *(fused_loss if fused_loss is not None else (None, None, None)))
+                        hs[1:], ms[1:], logit, out, *(fused_loss if fused_loss is not None else (None, None, None)), **lkw)
             if save:
                 ctx["loss_done"] = fused_loss is not None    # train_step: the broadcast MSE rode in the same launch
             x = hs[4]
@@ -1415,28 +1419,45 @@ class AVM(_LazyFlags, nn.Module):
     # ------------------------------------------------------------------------------------------
     # device-resident fused train step: forward, broadcast MSE, backward, Adam
     # ------------------------------------------------------------------------------------------
-    def train_step(self, audio, visual, labels, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, _loop_tick=(0, 0), _scatter=None):
+    def train_step(self, audio, visual, labels, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, _loop_tick=(0, 0), _scatter=None, *,
+                   loss="mse_bcast", loss_param=None, weights=None):
         """main.py:187-193 on GPU tensors. Returns (loss (1,), pred (N,)) as GPU tensors, no host sync.
+        `loss` (EXTENSION): "mse_bcast" is the reference's nn.MSELoss with its (n,1) x (n,) broadcast; "mse", "l1",
+        "smooth_l1" (loss_param = beta, default 1) are the per-frame losses mean(w_i l_i) with optional fp32 `weights` (N,); "rank" is the
+        pairwise logistic loss over the pairs with y_i > y_j. Up to 16 frames the loss rides in the fused MLP launch, above it is
+        ops.frame_loss; everything after dL/dpred is the same for every loss. Global-batch mode keeps the default loss.
         `_loop_tick`: (frames, sub-batches) the caller's loop counters advance by (loop.VideoTrainer); `_scatter(loss, pred)` -> row-copy
         segments (ops.rows_copy_batch form, cursors as they stand BEFORE the tick) that the step's last launch writes before it advances
         the counters (the per-video predictions / losses arrays of loop.VideoTrainer).
         fp32 steps of >= 256 frames in which every tensor trains and no gradient is exchanged (epi_fuse_dw_adam) update
         visbl.linear5.weight inside its weight-gradient GEMM: that tensor's slot of the gradient arena is then NOT written, and
         grad_of("visbl.linear5.weight") returns whatever an earlier backward left there. keep_ctx = True or epi_fuse = False keep it."""
+        loss_kind = loss
+        ops.loss_spec(loss_kind, loss_param, weights is not None, self.head)       # ValueError before anything is launched
+        n0 = visual.shape[0]
+        if weights is not None:
+            if not (torch.is_tensor(weights) and weights.dtype == F32 and weights.numel() == n0):
+                raise RuntimeError(f"weights must be a float32 tensor of {n0} elements")
+        if loss_kind != "mse_bcast" and self.stat_sync is not None:
+            raise GoalnetError("global-batch mode is defined for the broadcast MSE only: loss='mse_bcast'")
+        if weights is not None:
+            weights = weights.detach().to(self._device).reshape(-1).contiguous()
         frozen = self._frozen_names()                   # requires_grad=False: no gradient, no update, no step counted (DESIGN.md §4.11)
         self._check_freeze(frozen)
         plain = self._plain_step(frozen)                # every tensor trains under the global step count: today's launches
-        n0 = visual.shape[0]
         loss = torch.empty(1, dtype=F32, device=self._device)
         dout = torch.empty(n0 if self.head == "regression" else (n0, self.num_classes), dtype=F32, device=self._device)
         # the regression head's broadcast MSE is evaluated by the fused MLP launch itself where that launch exists (<= 16 rows)
         lab32 = labels if (torch.is_tensor(labels) and labels.dtype == F32 and labels.is_contiguous() and labels.is_cuda) else None
         fused_loss = (lab32, loss, dout) if (self.stat_sync is None and lab32 is not None and self._mlp_fused(n0)) else None
         # the dropout draw counter advances with the step's other counters, in the one launch at the end
-        out, ctx = self.forward_device(audio, visual, save=True, fused_loss=fused_loss, caller_ticks=True)
+        out, ctx = self.forward_device(audio, visual, save=True, fused_loss=fused_loss, caller_ticks=True,
+                                       fused_loss_kind=None if loss_kind == "mse_bcast" else (loss_kind, loss_param, weights))
         n = out.shape[0]
         if ctx["loss_done"]:
             pass
+        elif loss_kind != "mse_bcast":
+            ops.frame_loss(out, labels.to(device=self._device, dtype=F32).reshape(-1).contiguous(), loss, dout, loss_kind, loss_param, weights)
         elif self.head == "classifier":
             if self.stat_sync is not None:
                 raise GoalnetError("global-batch mode is defined for the regression head's broadcast MSE only")

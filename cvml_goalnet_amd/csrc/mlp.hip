@@ -14,7 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "mse.h"
+#include "loss.h"
 
 using namespace goalnet;
 
@@ -31,7 +31,9 @@ struct MlpFwdP {
     float* h[4];                                    // layer outputs (n, J[l]), contiguous
     float* mult[4];                                 // (pre-activation > 0) * mask, saved for backward (nullable)
     float* logit; float* out;                       // (n)
-    const float* labels; float* loss; float* dout;  // optional tail: the broadcast MSE of `out` against labels (n) and dL/dout
+    const float* labels; float* loss; float* dout;  // optional tail: the loss of `out` against labels (n) and dL/dout
+    int loss_kind; double loss_param;               // GOALNET_LOSS_* (goalnet_loss.h): the broadcast MSE unless goalnet_mlp_fwd_loss says otherwise
+    const float* weights;                           // per-frame weights of the pointwise kinds (nullable)
     int n; int J[4];
     int* sync;                                      // [0] arrivals, [1] departures, [2] error flag; zero on entry / exit
 };
@@ -167,9 +169,11 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(MlpFwdP P) {
             }
         }
         if (P.labels) {
-            // nn.MSELoss on (n,1) x (n,) (main.py:191) in the same launch: this block wrote every out[m] itself
+            // nn.MSELoss on (n,1) x (n,) (main.py:191), or the loss goalnet_mlp_fwd_loss selected, in the same launch: this block
+            // wrote every out[m] itself
             __syncthreads();
-            mse_bcast_block(P.out, P.labels, P.n, P.loss, P.dout);
+            if (P.loss_kind == GOALNET_LOSS_MSE_BCAST) mse_bcast_block(P.out, P.labels, P.n, P.loss, P.dout);
+            else frame_loss_block(P.loss_kind, P.loss_param, P.out, P.labels, P.weights, P.n, P.loss, P.dout);
         }
     }
     grid_leave(P.sync, gridDim.x);
@@ -336,9 +340,10 @@ extern "C" {
 
 int goalnet_mlp_blocks(void) { return MLP_BLOCKS; }
 
-int goalnet_mlp_fwd(const float* cat, int64_t ldcat, int K0, const float* const* w, const float* const* b,
-                    const float* const* mask, const int64_t* ldmask, float* const* h, float* const* mult,
-                    float* logit, float* out, const float* labels, float* loss, float* dout, int n, int* sync, void* stream) {
+int goalnet_mlp_fwd_loss(const float* cat, int64_t ldcat, int K0, const float* const* w, const float* const* b,
+                         const float* const* mask, const int64_t* ldmask, float* const* h, float* const* mult,
+                         float* logit, float* out, const float* labels, float* loss, float* dout,
+                         int loss_kind, double loss_param, const float* weights, int n, int* sync, void* stream) {
     GN_REQUIRE(cat && w && b && mask && ldmask && h && mult && logit && out && sync, GOALNET_E_NULL, "mlp_fwd: null pointer");
     GN_REQUIRE(n >= 1 && n <= 16, GOALNET_E_SHAPE, "mlp_fwd: 1..16 rows (the reference's sub-batches)");
     GN_REQUIRE(K0 > 0 && K0 <= KMAX && K0 % 4 == 0, GOALNET_E_SHAPE, "mlp_fwd: K0 must be a multiple of 4, <= 640");
@@ -355,7 +360,9 @@ int goalnet_mlp_fwd(const float* cat, int64_t ldcat, int K0, const float* const*
         P.mask[l] = mask[l]; P.ldmask[l] = ldmask[l]; P.h[l] = h[l]; P.mult[l] = mult[l]; P.J[l] = J[l];
     }
     GN_REQUIRE(!labels || (loss || dout), GOALNET_E_NULL, "mlp_fwd: labels without a loss / dout destination");
+    if (const int rc = loss_args_ok("mlp_fwd", loss_kind, loss_param, weights)) return rc;
     P.logit = logit; P.out = out; P.labels = labels; P.loss = loss; P.dout = dout; P.n = n; P.sync = sync;
+    P.loss_kind = loss_kind; P.loss_param = loss_param; P.weights = weights;
     hipStream_t st = (hipStream_t)stream;
     static const int fb = getenv("GOALNET_MLP_FWD_BLOCKS") ? atoi(getenv("GOALNET_MLP_FWD_BLOCKS")) : MLP_FWD_BLOCKS;      // 16 | 32 | 64 (A/B runs)
 #define GN_MLP_FWD(MRV)                                                                                       \
@@ -371,6 +378,13 @@ int goalnet_mlp_fwd(const float* cat, int64_t ldcat, int K0, const float* const*
 #undef GN_MLP_FWD
     GN_LAUNCH_CHECK("mlp_fwd");
     return 0;
+}
+
+int goalnet_mlp_fwd(const float* cat, int64_t ldcat, int K0, const float* const* w, const float* const* b,
+                    const float* const* mask, const int64_t* ldmask, float* const* h, float* const* mult,
+                    float* logit, float* out, const float* labels, float* loss, float* dout, int n, int* sync, void* stream) {
+    return goalnet_mlp_fwd_loss(cat, ldcat, K0, w, b, mask, ldmask, h, mult, logit, out, labels, loss, dout, GOALNET_LOSS_MSE_BCAST, 0.0,
+                                nullptr, n, sync, stream);
 }
 
 size_t goalnet_mlp_bwd_ws_bytes(int n) { return (size_t)n * (512 + 512 + 256 + 128) * sizeof(float); }

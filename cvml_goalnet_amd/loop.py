@@ -35,14 +35,17 @@ F32 = torch.float32
 
 class VideoTrainer:
     def __init__(self, model, subbatch_size: int = 10, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 graphs: bool = True):
+                 graphs: bool = True, loss: str = "mse_bcast", loss_param=None):
         if subbatch_size < 1:
             raise ValueError("subbatch_size must be >= 1")
+        ops.loss_spec(loss, loss_param, False, model.head)      # ValueError: unknown name, beta <= 0, the classifier head
+        self.loss, self.loss_param = loss, loss_param           # AVM.train_step's loss; the default is the reference's
+        self._weighted = False                                  # the video being trained on came with per-frame weights
         self.model = model
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -69,6 +72,8 @@ class VideoTrainer:
         self._vid = torch.empty(cap, 3, hw[0], hw[1], dtype=F32, device=dev)
         self._aud = torch.empty(cap, 30, bins, dtype=F32, device=dev) if m.audio_included else None
         self._lab = torch.empty(cap, dtype=F32, device=dev)
+        # per-frame loss weights (train_video(weights=...)): only the pointwise losses take any
+        self._wts = torch.empty(cap, dtype=F32, device=dev) if self.loss not in ("mse_bcast", "rank") else None
         self._pred = torch.empty(cap, dtype=F32, device=dev)
         self._loss = torch.empty((cap + sb - 1) // sb + 1, dtype=F32, device=dev)
 
@@ -85,7 +90,14 @@ class VideoTrainer:
         if m.audio_included:
             aud = torch.empty(n, 30, bins, dtype=F32, device=dev)
             segs.append((self._aud, aud, n, st[2], 0, True))
-        ops.rows_copy_batch(segs)                                       # frames[a:b], labels[a:b], audios[a:b]
+        lkw = {}
+        if self.loss != "mse_bcast":
+            wts = None
+            if self._weighted:
+                wts = torch.empty(n, dtype=F32, device=dev)
+                segs.append((self._wts, wts, n, st[2], 0, True))
+            lkw = dict(loss=self.loss, loss_param=self.loss_param, weights=wts)
+        ops.rows_copy_batch(segs)                                       # frames[a:b], labels[a:b], audios[a:b], weights[a:b]
         # train_step advances all four counters in its last launch: cursor += n, sub-batch index += 1
         if m.head == "classifier":
             loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1))
@@ -96,7 +108,7 @@ class VideoTrainer:
         # regression head: that same last launch first writes predictions.extend(...), losses.append(...) at the positions the step
         # started from (main.py:195-196), then moves the counters
         m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1),
-                     _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)])
+                     _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)], **lkw)
 
     def _host_bookkeeping_after_replay(self):
         """What an eager train_step does on the host besides launching kernels."""
@@ -121,7 +133,8 @@ class VideoTrainer:
         # Freezing (requires_grad=False) prunes the backward and bakes the fused Adam's ranges with their step counts into the launch:
         # the key carries them (() while everything trains), so a changed trainable set is captured afresh and never replays a stale
         # graph. While the set is stable the counts of its ranges are too — only frozen tensors sit steps out — and replays stay valid.
-        gkey = (n, m._loss_scale_for(n), m.trainable_signature(), m.training)
+        # The loss is baked in too (its kind and beta are launch arguments, the weights a gathered segment): the key carries it.
+        gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted), m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -166,13 +179,14 @@ class VideoTrainer:
         self.replays += 1
 
     # ---- validation pass ---------------------------------------------------------------------------------------------
-    def eval_video(self, val_audios, val_frames, val_labels):
+    def eval_video(self, val_audios, val_frames, val_labels, weights=None):
         """main.py:218-226 for one video: the whole video in ONE forward under no_grad, then nn.MSELoss with its (n,1) x (n,)
-        broadcast. The forward follows the model's mode: in train mode (the reference's, it never calls .eval()) BatchNorm uses
-        batch statistics and updates its running buffers and dropout is live; after model.eval() BatchNorm uses the running
+        broadcast — or the trainer's `loss`, with optional per-frame `weights` (N,) for its pointwise kinds.
+        The forward follows the model's mode: in train mode (the reference's, it never calls .eval()) BatchNorm uses batch statistics and updates its running buffers and dropout is live; after model.eval() BatchNorm uses the running
         statistics, nothing is updated and dropout is off. Returns (loss (1,), predictions (N,)) as GPU tensors; nothing has
         been synchronised."""
         m = self.model
+        weights = self._check_weights(weights, val_frames.shape[0] if torch.is_tensor(val_frames) else 0)
         m._require_device()
         aud, vis, _ = m._to_device_inputs(val_audios, val_frames)
         lab = torch.as_tensor(val_labels).detach().to(device=m._device, dtype=F32).reshape(-1).contiguous()
@@ -184,15 +198,28 @@ class VideoTrainer:
         if m.head == "classifier":
             ops.cross_entropy(out, lab, loss, None)                     # main.py:96-97
             return loss, ops.argmax_plus1(out, torch.empty(lab.numel(), dtype=F32, device=m._device))
+        if self.loss != "mse_bcast":
+            ops.frame_loss(out, lab, loss, None, self.loss, self.loss_param, None if weights is None else weights.to(m._device))
+            return loss, out
         ops.mse_bcast(out, lab, loss, None)
         return loss, out
 
+    def _check_weights(self, weights, n_frames):
+        """per-frame loss weights of one video: ValueError where the trainer's loss takes none, RuntimeError on a wrong shape / dtype"""
+        if weights is None:
+            return None
+        ops.loss_spec(self.loss, self.loss_param, True, self.model.head)
+        if not (torch.is_tensor(weights) and weights.dtype == F32 and weights.numel() == n_frames):
+            raise RuntimeError(f"weights must be a float32 tensor of {n_frames} elements")
+        return weights.detach().reshape(-1).contiguous()
+
     # ---- the loop ------------------------------------------------------------------------------------------------
-    def train_video(self, batch_audios, batch_frames, batch_labels):
+    def train_video(self, batch_audios, batch_frames, batch_labels, weights=None):
         """One video (main.py:169-203). batch_frames (N,3,H,W), batch_audios (N,30,B) or a list of None,
-        batch_labels (N,) — CPU or GPU tensors. Returns (losses (S,), predictions (N,)) as GPU tensors with
-        S = ceil(N / subbatch_size); nothing has been synchronised. `losses.mean()` is main.py:203's batch_loss."""
+        batch_labels (N,), weights (N,) float32 or None (the trainer's pointwise losses) — CPU or GPU tensors.
+        Returns (losses (S,), predictions (N,)) as GPU tensors with S = ceil(N / subbatch_size); nothing has been synchronised. `losses.mean()` is main.py:203's batch_loss."""
         m = self.model
+        weights = self._check_weights(weights, batch_frames.shape[0] if torch.is_tensor(batch_frames) else 0)
         m._require_device()
         if not torch.is_tensor(batch_frames) or batch_frames.dim() != 4 or batch_frames.shape[1] != 3:
             raise RuntimeError("batch_frames must be a (N,3,H,W) tensor")
@@ -209,6 +236,9 @@ class VideoTrainer:
         self._ensure_tables(n_frames, tuple(batch_frames.shape[2:]), bins)
         self._vid[:n_frames].copy_(batch_frames, non_blocking=True)
         self._lab[:n_frames].copy_(batch_labels.reshape(-1), non_blocking=True)
+        self._weighted = weights is not None
+        if weights is not None:
+            self._wts[:n_frames].copy_(weights, non_blocking=True)
         if m.audio_included:
             self._aud[:n_frames].copy_(batch_audios, non_blocking=True)
         if m._state is None:

@@ -729,11 +729,56 @@ def _ptrs(ts):
     return (ctypes.c_void_p * len(ts))(*[_p(t) for t in ts])
 
 
-def mlp_fwd(cat, ws, bs, masks, hs, mults, logit, out, labels=None, loss=None, dout=None):
+def loss_spec(kind="mse_bcast", param=None, weights_given=False, head="regression"):
+    """Validate a loss selection (include/goalnet_loss.h) on the host, before any launch: -> (GOALNET_LOSS_* code, param as float).
+    ValueError: an unknown name, smooth_l1's beta <= 0, weights with a loss that takes none, a non-default loss on the classifier head."""
+    if kind not in _lib.LOSS_KINDS:
+        raise ValueError(f"unknown loss {kind!r}: one of {', '.join(_lib.LOSS_KINDS)}")
+    if kind != "mse_bcast" and head != "regression":
+        raise ValueError(f"loss={kind!r} is defined for the regression head; head='classifier' trains with its cross-entropy")
+    p = 0.0
+    if kind == "smooth_l1":
+        p = 1.0 if param is None else float(param)
+        if not p > 0.0:
+            raise ValueError(f"smooth_l1 needs beta > 0, got {param!r}")
+    if weights_given and kind in ("mse_bcast", "rank"):
+        raise ValueError(f"loss={kind!r} takes no per-frame weights")
+    return _lib.LOSS_KINDS[kind], p
+
+
+def _loss_weights_ok(weights, n, who):
+    _req(weights is None or (torch.is_tensor(weights) and weights.dtype == F32 and weights.numel() == n and weights.is_contiguous()),
+         f"{who}: weights must be a contiguous float32 tensor of {n} elements")
+
+
+def frame_loss(pred, labels, loss, dpred, kind, param=None, weights=None):
+    """loss (1) and dpred (n) — each optional, not both — of the named loss (loss_spec) for pred (n) against labels (n), fp32 GPU
+    tensors; weights (n) for the pointwise kinds. The rank loss is O(n^2) and borrows a workspace of 24 n bytes."""
+    code, p = loss_spec(kind, param, weights is not None)
+    n = pred.numel()
+    _req(1 <= n <= _lib.FRAME_LOSS_MAX_N, f"frame_loss: 1..{_lib.FRAME_LOSS_MAX_N} predictions")
+    _loss_weights_ok(weights, n, "frame_loss")
+    _req(loss is not None or dpred is not None, "frame_loss: neither loss nor dpred")
+    _chk(pred, labels, loss, dpred, weights)
+    _req(labels.numel() == n and pred.dtype == F32 and labels.dtype == F32 and pred.is_contiguous() and labels.is_contiguous(),
+         "frame_loss: pred and labels must be contiguous float32 tensors of the same length")
+    _req((loss is None or (loss.dtype == F32 and loss.numel() >= 1)) and (dpred is None or (dpred.dtype == F32 and dpred.numel() == n and dpred.is_contiguous())),
+         "frame_loss: loss (1) / dpred (n) must be contiguous float32 tensors")
+    nbytes = lib().goalnet_frame_loss_ws_bytes(code, n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=pred.device) if nbytes else None
+    check(lib().goalnet_frame_loss(code, p, pred.data_ptr(), labels.data_ptr(), _p(weights), n, _p(loss), _p(dpred), _p(ws), nbytes, _s()),
+          "frame_loss")
+
+
+def mlp_fwd(cat, ws, bs, masks, hs, mults, logit, out, labels=None, loss=None, dout=None, *, loss_kind="mse_bcast", loss_param=None,
+            weights=None):
     """fusion.0 .. fusion.12 + Sigmoid + 4y+1 on <= 16 rows in one launch. cat (n, K0) may be a view with a row stride;
-    ws / bs: 5 weights / biases; masks: 4 dropout multipliers or None; hs: 4 outputs; mults: 4 saved multipliers or None"""
-    _chk(cat, logit, out, labels, loss, dout, *ws, *bs, *masks, *hs, *mults)
+    ws / bs: 5 weights / biases; masks: 4 dropout multipliers or None; hs: 4 outputs; mults: 4 saved multipliers or None.
+    labels: the launch's tail evaluates the loss too — the broadcast MSE (goalnet_mlp_fwd) or the named one (goalnet_mlp_fwd_loss)."""
+    code, lparam = loss_spec(loss_kind, loss_param, weights is not None)
+    _chk(cat, logit, out, labels, loss, dout, weights, *ws, *bs, *masks, *hs, *mults)
     n, K0 = cat.shape
+    _loss_weights_ok(weights, n, "mlp_fwd")
     _req(labels is None or (labels.numel() == n and labels.dtype == F32 and labels.is_contiguous() and loss is not None and dout is not None
                             and dout.numel() == n), "mlp_fwd: labels (n) need loss (1) and dout (n)")
     _req(len(ws) == 5 and len(bs) == 5 and len(masks) == 4 and len(hs) == 4 and len(mults) == 4, "mlp_fwd: 5 layers, 4 hidden outputs")
@@ -745,8 +790,13 @@ def mlp_fwd(cat, ws, bs, masks, hs, mults, logit, out, labels=None, loss=None, d
     _req(ws[4].numel() == 128 and bs[4].numel() == 1 and logit.numel() == n and out.numel() == n, "mlp_fwd: head shapes")
     ldm = (ctypes.c_int64 * 4)(*[0 if m is None else _ld(m) for m in masks])
     sync = _tile_counters(("mlp_fwd", n, K0), cat.device)
-    check(lib().goalnet_mlp_fwd(cat.data_ptr(), _ld(cat), K0, _ptrs(ws), _ptrs(bs), _ptrs(masks), ldm, _ptrs(hs), _ptrs(mults),
-                                logit.data_ptr(), out.data_ptr(), _p(labels), _p(loss), _p(dout), n, sync.data_ptr(), _s()), "mlp_fwd")
+    if loss_kind == "mse_bcast":
+        check(lib().goalnet_mlp_fwd(cat.data_ptr(), _ld(cat), K0, _ptrs(ws), _ptrs(bs), _ptrs(masks), ldm, _ptrs(hs), _ptrs(mults),
+                                    logit.data_ptr(), out.data_ptr(), _p(labels), _p(loss), _p(dout), n, sync.data_ptr(), _s()), "mlp_fwd")
+        return
+    check(lib().goalnet_mlp_fwd_loss(cat.data_ptr(), _ld(cat), K0, _ptrs(ws), _ptrs(bs), _ptrs(masks), ldm, _ptrs(hs), _ptrs(mults),
+                                     logit.data_ptr(), out.data_ptr(), _p(labels), _p(loss), _p(dout), code, lparam, _p(weights), n,
+                                     sync.data_ptr(), _s()), "mlp_fwd_loss")
 
 
 def mlp_bwd(dout, out, xs, ms, ws, dws, dbs, dcat, db5, voff):

@@ -680,6 +680,123 @@ __device__ __forceinline__ void store_acc_n64(const EpiP& ep, const f32x16 (&acc
     }
 }
 
+// ---- the epilogue on buffer stores ------------------------------------------------------------------------------------------
+// store_acc / store_acc_n64 recompute row * ld + col in 64 bits, compare a 64-bit row and branch for every one of a lane's 64 (32)
+// stores: 367 (EPI_RAW) to 510 (EPI_BIAS_RELU) VALU instructions per wave and tile, 128 of them quarter-rate integer multiplies,
+// and the fp32 MFMA shares its SIMD's issue slots with them (operand loaders, above). Here the stores go the loaders' way:
+//   * one buffer resource per block, based at the tile's first output row, num_records = the tile's true extent
+//     ((nrows - 1) ld + cols floats): whatever the addressing does, a store cannot leave the tile's own rows;
+//   * the lane's part of the address is a loop-invariant voffset per fragment column (row-in-tile * ld + col, OOB when col >= cols:
+//     the range check drops the store), the register's row term (32 fm + (e & 3) + 8 (e >> 2)) ld a scalar offset (SALU);
+//   * rows: a tile with all its 128 rows inside the matrix (FULL) stores unconditionally, every row offset being inside num_records
+//     by construction; the ragged last row tile selects OOB into the voffset per store. So no result depends on whether the scalar
+//     offset takes part in the range check.
+// The values are store_acc's: acc, or fmaxf(acc + bias, lo). epi_store_mode() (host) admits EPI_RAW (slabs included) and
+// EPI_BIAS_RELU with 128 rows of ld inside one resource; everything else keeps store_acc.
+// For a K-contiguous A operand only (fragment fm holds the rows fm * 32 + i). The kernels whose A is row-contiguous, the weight
+// gradients, keep store_acc: their gain stayed inside the run-to-run spread, and with the second epilogue compiled in the one-stage
+// forms (128 registers) reloaded one more spilled offset per K-tile (profiles/epi_store_kernel_stats.md).
+// `pair` (B read row-contiguous = linear dX: a lane's fragments fn = 0, 1 are the adjacent columns 2r, 2r + 1, and cols % 4 == 0
+// puts both on the same side of `cols`): one 8-byte store for the two, 256 contiguous bytes per row and half-wave (as adam_acc).
+enum { EPI_ST_GLOBAL = 0, EPI_ST_BUF = 1, EPI_ST_BUF_PAIR = 2 };
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+template <bool FULL>
+__device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t rs, float v, unsigned voff, unsigned soff, int rl, int nrows) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, (int)((FULL || rl < nrows) ? voff : OOB), (int)soff, 0);
+}
+
+template <bool BIL, bool FULL>
+__device__ __forceinline__ void store_acc_buf(const EpiP& ep, const f32x16 (&acc)[2][2], int tm, int tn, int split, int pair,
+                                              int wm, int wn, int r, int h) {
+    const bool slab = ep.slab_stride > 0;
+    float* outp = slab ? (ep.slabs ? ep.slabs : ep.out) + (int64_t)split * ep.slab_stride : ep.out;
+    const int64_t ld = (slab && ep.slabs) ? (int64_t)ep.cols : ep.ld;
+    const int64_t trow0 = (int64_t)tm * BM;
+    const int nrows = FULL ? BM : (int)(ep.rows - trow0);
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(outp + trow0 * ld, (uint32_t)(((int64_t)(nrows - 1) * ld + ep.cols) * 4));
+    const unsigned ld4 = (unsigned)ld * 4u;
+    const int rl0 = wm * 64 + 4 * h;                                  // the lane's first row in the tile (fragment fm = 0)
+    unsigned voff[2];
+    float bv[2];
+    const bool relu_mode = !slab && ep.mode == EPI_BIAS_RELU;
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn) {
+        const int col = tn * BN + wn * 64 + (BIL ? 2 * r + fn : fn * 32 + r);
+        voff[fn] = col < ep.cols ? (unsigned)rl0 * ld4 + (unsigned)col * 4u : OOB;
+        bv[fn] = (relu_mode && ep.bias) ? ep.bias[col < ep.cols ? col : 0] : 0.f;
+    }
+    if (relu_mode) {
+        const float lo = ep.relu ? 0.f : -INFINITY;
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+            for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int dr = fm * 32 + (e & 3) + 8 * (e >> 2);
+                    bstore<FULL>(rs, fmaxf(acc[fm][fn][e] + bv[fn], lo), voff[fn], (unsigned)dr * ld4, rl0 + dr, nrows);
+                }
+        return;
+    }
+    if constexpr (BIL) {
+        if (pair) {
+#pragma unroll
+            for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int dr = fm * 32 + (e & 3) + 8 * (e >> 2);
+                    const u32x2 v = {__float_as_uint(acc[fm][0][e]), __float_as_uint(acc[fm][1][e])};
+                    __builtin_amdgcn_raw_buffer_store_b64(v, rs, (int)((FULL || rl0 + dr < nrows) ? voff[0] : OOB), (int)((unsigned)dr * ld4), 0);
+                }
+            return;
+        }
+    }
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int dr = fm * 32 + (e & 3) + 8 * (e >> 2);
+                bstore<FULL>(rs, acc[fm][fn][e], voff[fn], (unsigned)dr * ld4, rl0 + dr, nrows);
+            }
+}
+
+// the same for the 128 x 64 tile (store_acc_n64): the wave's rows are wave * 32 + 4 h + (e & 3) + 8 (e >> 2)
+template <bool FULL>
+__device__ __forceinline__ void store_acc_n64_buf(const EpiP& ep, const f32x16 (&acc)[2], int tm, int tn, int split, int wave, int r, int h) {
+    const bool slab = ep.slab_stride > 0;
+    float* outp = slab ? (ep.slabs ? ep.slabs : ep.out) + (int64_t)split * ep.slab_stride : ep.out;
+    const int64_t ld = (slab && ep.slabs) ? (int64_t)ep.cols : ep.ld;
+    const int64_t trow0 = (int64_t)tm * BM;
+    const int nrows = FULL ? BM : (int)(ep.rows - trow0);
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(outp + trow0 * ld, (uint32_t)(((int64_t)(nrows - 1) * ld + ep.cols) * 4));
+    const unsigned ld4 = (unsigned)ld * 4u;
+    const int rl0 = wave * 32 + 4 * h;
+    const bool relu_mode = !slab && ep.mode == EPI_BIAS_RELU;
+    const float lo = (relu_mode && ep.relu) ? 0.f : -INFINITY;
+#pragma unroll
+    for (int fn = 0; fn < 2; ++fn) {
+        const int col = tn * 64 + fn * 32 + r;
+        const unsigned voff = col < ep.cols ? (unsigned)rl0 * ld4 + (unsigned)col * 4u : OOB;
+        const float bv = (relu_mode && ep.bias) ? ep.bias[col < ep.cols ? col : 0] : 0.f;
+        if (relu_mode) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int dr = (e & 3) + 8 * (e >> 2);
+                bstore<FULL>(rs, fmaxf(acc[fn][e] + bv, lo), voff, (unsigned)dr * ld4, rl0 + dr, nrows);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int dr = (e & 3) + 8 * (e >> 2);
+                bstore<FULL>(rs, acc[fn][e], voff, (unsigned)dr * ld4, rl0 + dr, nrows);
+            }
+        }
+    }
+}
+
 // The K loop of one output tile as a function: loaders, LDS staging and MFMAs for K-tiles [kt0, kt1) of tile (tm, tn) into the
 // wave's 2 x 2 accumulator tiles (128 x 128 tile, per-K-tile loaders). gemm_f32_epi_kernel runs it; gemm_f32_kernel keeps its own
 // inline copy of the same statements: calling this function from it changed the register allocation of every instantiation
@@ -750,8 +867,11 @@ __device__ __forceinline__ void gemm_mainloop(const typename AL::P& ap, const ty
 // (122.0 -> 131.9); outputs bit-identical.
 template <class AL, class BL, bool N64 = false, int STAGES = 2>
 __global__ __launch_bounds__(256, STAGES == 1 ? (N64 ? 4 : AL::ONE_STAGE_BLOCKS) : 2) void gemm_f32_kernel(typename AL::P ap, typename BL::P bp, EpiP ep,
-                                                          int tiles_m, int tiles_n, int m_fast,
+                                                          int tiles_m, int tiles_n, int flags,
                                                           int ktiles, int ktiles_per_split, int xcd_splits) {
+    // flags: bit 0 = tiles walk M fastest, bits 1.. = EPI_ST_* (one word, so that the kernels keep their signature and with it
+    // the names the profiles and bench.py know them by)
+    const int m_fast = flags & 1, epi_st = flags >> 1;
     const int tid = threadIdx.x;
     int tm, tn, split;
     if (xcd_splits > 0) {
@@ -837,8 +957,18 @@ __global__ __launch_bounds__(256, STAGES == 1 ? (N64 ? 4 : AL::ONE_STAGE_BLOCKS)
             __syncthreads();
         }
     }
-    if constexpr (N64) store_acc_n64(ep, acc[0], tm, tn, split, wave, r, h);
-    else store_acc<!AL::KC, !BL::KC>(ep, acc, tm, tn, split, wm, wn, r, h);
+    const bool full = (int64_t)tm * BM + BM <= ep.rows;      // wave-uniform, as epi_st: one epilogue per block
+    if constexpr (N64) {
+        if (epi_st == EPI_ST_GLOBAL) store_acc_n64(ep, acc[0], tm, tn, split, wave, r, h);
+        else if (full) store_acc_n64_buf<true>(ep, acc[0], tm, tn, split, wave, r, h);
+        else store_acc_n64_buf<false>(ep, acc[0], tm, tn, split, wave, r, h);
+    } else if constexpr (!AL::KC) {                          // the weight gradients: store_acc only (see store_acc_buf)
+        store_acc<true, !BL::KC>(ep, acc, tm, tn, split, wm, wn, r, h);
+    } else {
+        if (epi_st == EPI_ST_GLOBAL) store_acc<false, !BL::KC>(ep, acc, tm, tn, split, wm, wn, r, h);
+        else if (full) store_acc_buf<!BL::KC, true>(ep, acc, tm, tn, split, epi_st == EPI_ST_BUF_PAIR, wm, wn, r, h);
+        else store_acc_buf<!BL::KC, false>(ep, acc, tm, tn, split, epi_st == EPI_ST_BUF_PAIR, wm, wn, r, h);
+    }
     if (ep.tile_ctr) {                                       // fused split-K reduction: the tile's last block sums the slabs
         const int nsp = (ktiles + ktiles_per_split - 1) / ktiles_per_split;
         fused_splitk_reduce<N64 ? 64 : BN>(ep, tm, tn, tm * tiles_n + tn, nsp, tid);
@@ -1011,6 +1141,23 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(const float* sl
     }
 }
 
+// Which epilogue a launch takes (store_acc_buf, above). The buffer stores serve what a tile with a K-contiguous A operand writes as
+// EPI_RAW (slabs included) or EPI_BIAS_RELU when 128 rows of the output's leading dimension fit one buffer resource; a wider `ld`,
+// EPI_MUL / EPI_FULL and a row-contiguous A (the weight gradients) keep store_acc. 8-byte stores for linear dX, the role where they measured faster (profiles/epi_store_kernel_stats.md). GOALNET_F32_EPI_STORE,
+// read per call: 0 forces store_acc everywhere, 1 the 4-byte buffer stores everywhere they apply (tests, A/B runs).
+constexpr bool EPI_PAIR_DX = true;           // A K-contiguous, B row-contiguous: linear dX
+static int epi_store_mode(const EpiP& ep, bool a_kc, bool b_kc) {
+    const char* e = getenv("GOALNET_F32_EPI_STORE");
+    if ((e && e[0] == '0') || !a_kc) return EPI_ST_GLOBAL;
+    const bool slab = ep.slab_stride > 0;
+    const int mode = slab ? EPI_RAW : ep.mode;
+    const int64_t ld = (slab && ep.slabs) ? (int64_t)ep.cols : ep.ld;
+    if (mode != EPI_RAW && mode != EPI_BIAS_RELU) return EPI_ST_GLOBAL;
+    if (ep.rows <= 0 || ep.cols <= 0 || ld < ep.cols || (int64_t)BM * ld * 4 >= 0xFFFFFF00ll) return EPI_ST_GLOBAL;
+    if (e && e[0] == '1') return EPI_ST_BUF;
+    return (EPI_PAIR_DX && !b_kc && mode == EPI_RAW) ? EPI_ST_BUF_PAIR : EPI_ST_BUF;
+}
+
 template <class AL, class BL, bool N64 = false>
 int launch_gemm(const char* name, const typename AL::P& ap, const typename BL::P& bp, const EpiP& ep,
                 int64_t M, int64_t N, int ktiles, int nsplit, int m_fast, hipStream_t st) {
@@ -1029,16 +1176,17 @@ int launch_gemm(const char* name, const typename AL::P& ap, const typename BL::P
     // 91.3 -> 96.1; linear5 forward 121.9 -> 99.7 and dX 116.4 -> 114.7 (a K-contiguous A operand with a 10 MB row stride): by
     // the A loader's trait. GOALNET_F32_STAGES=1|2 forces one form (tests, A/B runs).
     static const int force_stages = getenv("GOALNET_F32_STAGES") ? atoi(getenv("GOALNET_F32_STAGES")) : 0;
+    const int epi_st = epi_store_mode(ep, AL::KC, BL::KC);
     const bool one_stage = AL::STRIP || force_stages == 1 || (force_stages != 2 && AL::ONE_STAGE);     // the strip form has no two-stage variant
     if (one_stage) {        // the 128 x 64 tile as well: conv2's data gradient 108.9 -> 123.1 TF/s
         hipLaunchKernelGGL((gemm_f32_kernel<AL, BL, N64, 1>), grid, dim3(256), 0, st, ap, bp, ep, (int)tiles_m, (int)tiles_n,
-                           m_fast, ktiles, kps, xcd_local ? nsplit : 0);
+                           (m_fast & 1) | (epi_st << 1), ktiles, kps, xcd_local ? nsplit : 0);
         GN_LAUNCH_CHECK(name);
         return 0;
     }
     if constexpr (!AL::STRIP) {
         hipLaunchKernelGGL((gemm_f32_kernel<AL, BL, N64>), grid, dim3(256), 0, st, ap, bp, ep, (int)tiles_m, (int)tiles_n,
-                           m_fast, ktiles, kps, xcd_local ? nsplit : 0);
+                           (m_fast & 1) | (epi_st << 1), ktiles, kps, xcd_local ? nsplit : 0);
         GN_LAUNCH_CHECK(name);
     }
     return 0;

@@ -25,6 +25,12 @@ class RowCopy(ctypes.Structure):
                 ("cursor_bias", c_int64)]
 
 
+class RowCopyIndexed(ctypes.Structure):
+    """goalnet_rowcopy_indexed (include/goalnet_epoch.h)"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_bytes", c_int64), ("nrows", c_int), ("gather", c_int), ("cursor", c_void_p),
+                ("cursor_bias", c_int64), ("indexed", c_int), ("table_rows", c_int64)]
+
+
 class AdamRange(ctypes.Structure):
     """goalnet_adam_range (include/goalnet_hip.h)"""
     _fields_ = [("begin", c_int64), ("count", c_int64), ("skipped", c_int64)]
@@ -179,6 +185,19 @@ LOSS_PROTOTYPES = {
 LOSS_KINDS = {"mse_bcast": 0, "mse": 1, "l1": 2, "smooth_l1": 3, "rank": 4}
 FRAME_LOSS_MAX_N = 65536
 
+
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_epoch.h, the third public header (shuffled,
+# augmented passes over a resident video): additions again, the first two tables stay as they are
+EPOCH_PROTOTYPES = {
+    "goalnet_epoch_plan": (c_int, [P, c_int, c_uint64, c_uint32, c_int, c_float, c_int, c_float, c_float, P]),
+    "goalnet_frames_gather_aug": (c_int, [P, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int, P]),
+    "goalnet_rows_copy_indexed": (c_int, [ctypes.POINTER(RowCopyIndexed), c_int, P, c_int, P]),
+}
+EPOCH_MAX_N = 65536       # GOALNET_EPOCH_MAX_N
+PLAN_WORDS = 8            # GOALNET_PLAN_WORDS
+MAX_SHIFT = 32767         # GOALNET_MAX_SHIFT
+ROWCOPY_MAX = 4           # GOALNET_ROWCOPY_MAX
+
 _lib = None
 
 
@@ -196,7 +215,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items()):
+    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -21,6 +21,9 @@ sub-batch uses a second graph captured for its own size. The host reads results 
 The first sub-batch of each size runs eagerly (it is a real step — it also allocates the optimizer state and the
 cached operand buffers); the graph is captured at the second occurrence. Capturing executes nothing, so the
 sequence of optimizer steps is exactly the reference's.
+
+EXTENSION (off by default): `shuffle=True` / `augment={...}` draw a plan per pass on the device — frame order, flip,
+shift, contrast, brightness per frame — and the same graphs gather their sub-batches through it; predictions come back in frame order.
 """
 from __future__ import annotations
 
@@ -28,16 +31,26 @@ from typing import Dict, Tuple
 
 import torch
 
-from . import ops
+from . import augment as _augment, ops, synth
 
 F32 = torch.float32
 
 
 class VideoTrainer:
     def __init__(self, model, subbatch_size: int = 10, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 graphs: bool = True, loss: str = "mse_bcast", loss_param=None):
+                 graphs: bool = True, loss: str = "mse_bcast", loss_param=None, shuffle: bool = False, augment=None,
+                 seed: int = synth.BASE_SEED):
         if subbatch_size < 1:
             raise ValueError("subbatch_size must be >= 1")
+        # EXTENSION: a fresh frame order and fresh pixels per pass, drawn on the device into a plan table that the
+        # captured graphs read. Off by default: with shuffle=False and no augmentation switched on, _sub_step is today's launches.
+        self.augment = _augment.augment_options(augment)        # ValueError: unknown option, value out of range
+        self.shuffle = bool(shuffle)
+        self.seed = int(seed)
+        self.passes = 0                                         # train_video calls so far = the pass index of the next plan
+        self._colour = self.augment["contrast"] > 0 or self.augment["brightness"] > 0
+        self._augments = self._colour or self.augment["flip_p"] > 0 or self.augment["max_shift"] > 0
+        self._planned = self.shuffle or self._augments          # sub-batches go through the plan
         ops.loss_spec(loss, loss_param, False, model.head)      # ValueError: unknown name, beta <= 0, the classifier head
         self.loss, self.loss_param = loss, loss_param           # AVM.train_step's loss; the default is the reference's
         self._weighted = False                                  # the video being trained on came with per-frame weights
@@ -45,7 +58,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -76,6 +89,8 @@ class VideoTrainer:
         self._wts = torch.empty(cap, dtype=F32, device=dev) if self.loss not in ("mse_bcast", "rank") else None
         self._pred = torch.empty(cap, dtype=F32, device=dev)
         self._loss = torch.empty((cap + sb - 1) // sb + 1, dtype=F32, device=dev)
+        # the pass plan (augment.py): rewritten eagerly by every train_video, read by the graphs at this address
+        self._plan = torch.zeros(cap, 8, dtype=torch.int32, device=dev) if self._planned else None
 
     def _sub_step(self, n: int):
         """gather rows -> train_step -> scatter results -> advance the counters. Pure device work (capturable)."""
@@ -85,6 +100,8 @@ class VideoTrainer:
         hw, bins = self._key
         vis = torch.empty(n, 3, hw[0], hw[1], dtype=F32, device=dev)
         lab = torch.empty(n, dtype=F32, device=dev)
+        if self._planned:
+            return self._sub_step_planned(n, vis, lab)
         segs = [(self._vid, vis, n, st[2], 0, True), (self._lab, lab, n, st[2], 0, True)]
         aud = None
         if m.audio_included:
@@ -110,6 +127,32 @@ class VideoTrainer:
         m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1),
                      _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)], **lkw)
 
+    def _sub_step_planned(self, n: int, vis, lab):
+        """_sub_step with the sub-batch taken through the pass plan: frames plan[cursor : cursor + n] in that order, augmented as their
+        rows say; labels, audio and weights follow the same order; the predictions go back to their frames' own positions."""
+        m = self.model
+        st = m._state
+        dev = m._device
+        ops.frames_gather_aug(self._vid, vis, self._plan, n, st[2], 0, self._colour)
+        segs = [(self._lab, lab, n, st[2], 0, True, True)]
+        aud = None
+        if m.audio_included:
+            aud = torch.empty(n, 30, self._key[1], dtype=F32, device=dev)
+            segs.append((self._aud, aud, n, st[2], 0, True, True))
+        lkw = {}
+        if self.loss != "mse_bcast":
+            wts = None
+            if self._weighted:
+                wts = torch.empty(n, dtype=F32, device=dev)
+                segs.append((self._wts, wts, n, st[2], 0, True, True))
+            lkw = dict(loss=self.loss, loss_param=self.loss_param, weights=wts)
+        ops.rows_copy_indexed(segs, self._plan)
+        # the step's last launch moves the counters; the results are then written at the positions the step started from
+        loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **lkw)
+        if m.head == "classifier":
+            pred = ops.argmax_plus1(pred, torch.empty(n, dtype=F32, device=dev))        # main.py:190
+        ops.rows_copy_indexed([(self._pred, pred, n, st[2], -n, False, True), (self._loss, loss, 1, st[3], -1, False, False)], self._plan)
+
     def _host_bookkeeping_after_replay(self):
         """What an eager train_step does on the host besides launching kernels."""
         m = self.model
@@ -134,7 +177,10 @@ class VideoTrainer:
         # the key carries them (() while everything trains), so a changed trainable set is captured afresh and never replays a stale
         # graph. While the set is stable the counts of its ranges are too — only frozen tensors sit steps out — and replays stay valid.
         # The loss is baked in too (its kind and beta are launch arguments, the weights a gathered segment): the key carries it.
-        gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted), m.training)
+        # (shuffle, colour, any-augment): which gather the graph holds; the draws themselves live in the plan table. The tests read
+        # k[0] as the size, k[3] as the loss and k[-1] as the mode, so the new field sits in front of the mode.
+        gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted),
+                (self.shuffle, self._colour, self._augments), m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -214,10 +260,14 @@ class VideoTrainer:
         return weights.detach().reshape(-1).contiguous()
 
     # ---- the loop ------------------------------------------------------------------------------------------------
-    def train_video(self, batch_audios, batch_frames, batch_labels, weights=None):
+    def train_video(self, batch_audios, batch_frames, batch_labels, weights=None, plan_index=None):
         """One video (main.py:169-203). batch_frames (N,3,H,W), batch_audios (N,30,B) or a list of None,
         batch_labels (N,), weights (N,) float32 or None (the trainer's pointwise losses) — CPU or GPU tensors.
-        Returns (losses (S,), predictions (N,)) as GPU tensors with S = ceil(N / subbatch_size); nothing has been synchronised. `losses.mean()` is main.py:203's batch_loss."""
+        Returns (losses (S,), predictions (N,)) as GPU tensors with S = ceil(N / subbatch_size); nothing has been synchronised. `losses.mean()` is main.py:203's batch_loss.
+        With shuffle / augment on, the pass follows the plan of index `self.passes` (or `plan_index`, to resume a run): sub-batch s
+        holds the frames plan[s * sb : (s + 1) * sb] names, `losses` is in sub-batch order and `predictions` in FRAME order."""
+        if plan_index is not None and (isinstance(plan_index, bool) or not isinstance(plan_index, int) or not 0 <= plan_index < (1 << 28)):
+            raise ValueError(f"plan_index must be an integer in [0, 2^28), got {plan_index!r}")
         m = self.model
         weights = self._check_weights(weights, batch_frames.shape[0] if torch.is_tensor(batch_frames) else 0)
         m._require_device()
@@ -244,6 +294,10 @@ class VideoTrainer:
         if m._state is None:
             m._make_state()
         m._state[2:4].zero_()                       # subbatch_offset, iterations (main.py:173-175)
+        index = self.passes if plan_index is None else plan_index
+        self.passes = index + 1
+        if self._planned:
+            ops.epoch_plan(self._plan, n_frames, self.seed, index, self.shuffle, **self.augment)
         if m.precision == "fp16":
             # the previous video's results have been read back by now (main.py:203): a cheap place to notice skipped steps and
             # halve the loss scale (AVM.update_loss_scale) — a static scale would otherwise stall training silently

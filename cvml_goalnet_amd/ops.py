@@ -1049,6 +1049,78 @@ def rows_scatter(block, table, nrows, cursor):
     check(lib().goalnet_rows_scatter(block.data_ptr(), table.data_ptr(), row_bytes, nrows, _ctr(cursor), _s()), "rows_scatter")
 
 
+# ---- shuffled, augmented passes over a resident video (include/goalnet_epoch.h, csrc/epoch.hip) ----------
+I32 = torch.int32
+
+
+def augment_spec(flip_p=0.0, max_shift=0, contrast=0.0, brightness=0.0):
+    """(flip_p, max_shift, contrast, brightness) as goalnet_epoch_plan takes them — ValueError on a value outside its range, before
+    any launch and without a GPU. The three floats are rounded to fp32 here: that is what the draws are defined on."""
+    if isinstance(max_shift, bool) or not isinstance(max_shift, int) or not 0 <= max_shift <= _lib.MAX_SHIFT:
+        raise ValueError(f"max_shift must be an integer in [0, {_lib.MAX_SHIFT}], got {max_shift!r}")
+    out = []
+    for name, v, ok in (("flip_p", flip_p, lambda f: 0.0 <= f <= 1.0), ("contrast", contrast, lambda f: 0.0 <= f < 1.0),
+                        ("brightness", brightness, lambda f: 0.0 <= f < float("inf"))):
+        try:
+            f = ctypes.c_float(float(v)).value
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {v!r}") from None
+        if not ok(f):                                   # NaN fails every comparison
+            raise ValueError(f"{name} = {v!r} is outside its range")
+        out.append(f)
+    return out[0], max_shift, out[1], out[2]
+
+
+def _plan_ok(plan, who):
+    _req(torch.is_tensor(plan) and plan.is_cuda and plan.dtype == I32 and plan.dim() == 2 and plan.shape[1] == _lib.PLAN_WORDS
+         and plan.is_contiguous() and plan.shape[0] >= 1, f"{who}: the plan must be a contiguous int32 (n, {_lib.PLAN_WORDS}) GPU tensor")
+
+
+def epoch_plan(plan, n, seed, index, shuffle=False, flip_p=0.0, max_shift=0, contrast=0.0, brightness=0.0):
+    """rows [0, n) of `plan` (int32 (>= n, 8)) = the plan of pass `index`: {src, flip, dx, dy, gain, bias, 0, 0} per consumed frame"""
+    flip_p, max_shift, contrast, brightness = augment_spec(flip_p, max_shift, contrast, brightness)
+    if not 1 <= n <= _lib.EPOCH_MAX_N:
+        raise ValueError(f"a pass takes 1..{_lib.EPOCH_MAX_N} frames, got {n}")
+    if not 0 <= index < (1 << 28):
+        raise ValueError(f"pass index must be in [0, 2^28), got {index}")
+    _plan_ok(plan, "epoch_plan")
+    _req(plan.shape[0] >= n, "epoch_plan: the plan table is shorter than the pass")
+    check(lib().goalnet_epoch_plan(plan.data_ptr(), n, int(seed) & 0xFFFFFFFFFFFFFFFF, index, 1 if shuffle else 0, flip_p, max_shift, contrast,
+                                   brightness, _s()), "epoch_plan")
+    return plan
+
+
+def frames_gather_aug(table, out, plan, nrows, cursor, cursor_bias=0, colour=False):
+    """out[i] = the frame plan[cursor + cursor_bias + i] names, flipped / shifted (edge-replicate) and, with `colour`, gain / bias /
+    clamp to [0, 1]; table (rows, C, H, W), out (nrows, C, H, W), fp32. One launch."""
+    _chk(table, out)
+    _plan_ok(plan, "frames_gather_aug")
+    _req(table.dtype == F32 and out.dtype == F32 and table.dim() == 4 and table.is_contiguous() and out.is_contiguous()
+         and tuple(out.shape) == (nrows,) + tuple(table.shape[1:]), "frames_gather_aug: fp32 (rows, C, H, W) table and (nrows, C, H, W) block")
+    _, C, H, W = table.shape
+    check(lib().goalnet_frames_gather_aug(table.data_ptr(), table.shape[0], out.data_ptr(), plan.data_ptr(), plan.shape[0], C, H, W, nrows,
+                                          _ctr(cursor), int(cursor_bias), 1 if colour else 0, _s()), "frames_gather_aug")
+    return out
+
+
+def rows_copy_indexed(segments, plan):
+    """rows_copy_batch through the plan's order: segments of (table, block, nrows, cursor, cursor_bias, gather, indexed). Indexed
+    gather: block[i] = table[plan[c + i].src]; indexed scatter: table[plan[c + i].src] = block[i]; not indexed: rows [c, c + nrows)
+    as rows_copy_batch. One launch for up to 4 segments."""
+    _plan_ok(plan, "rows_copy_indexed")
+    _req(1 <= len(segments) <= _lib.ROWCOPY_MAX, f"rows_copy_indexed: 1..{_lib.ROWCOPY_MAX} segments")
+    arr = (_lib.RowCopyIndexed * len(segments))()
+    for k, (table, block, nrows, cursor, bias, gather, indexed) in enumerate(segments):
+        _chk(table, block)
+        _req(table.is_contiguous() and block.is_contiguous() and table.dtype == block.dtype, "rows_copy_indexed: contiguous tensors of one dtype")
+        row_bytes = table[0].numel() * table.element_size() if table.dim() > 1 else table.element_size()
+        _req(block.numel() * block.element_size() == row_bytes * nrows, "rows_copy_indexed: block size")
+        src, dst = (table, block) if gather else (block, table)
+        arr[k] = _lib.RowCopyIndexed(src.data_ptr(), dst.data_ptr(), row_bytes, nrows, 1 if gather else 0, _ctr(cursor), int(bias),
+                                     1 if indexed else 0, table.shape[0])
+    check(lib().goalnet_rows_copy_indexed(arr, len(segments), plan.data_ptr(), plan.shape[0], _s()), "rows_copy_indexed")
+
+
 # ---- inference mode around the model (csrc/summary.hip) ---------------------------------------------------------------------
 def frames_preprocess_strided(frames, stride, out, minmax):
     """out (n, 3, H, W) fp32 = frames_preprocess of frames[::stride], n = ceil(n_total / stride), read in place from the whole

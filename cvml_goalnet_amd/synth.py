@@ -84,6 +84,7 @@ TID_LABELS = 6
 TID_DROP = 4096  # + 8*step + layer: visbl.drop5, fusion.2, fusion.5, fusion.8, fusion.11
 TID_PARAM = 64  # 64 + index into PARAM_ORDER
 TID_GRADOUT = 40
+TID_PLAN = 1 << 30  # + 8*pass + option: order, flip, dx, dy, gain, bias of a shuffled / augmented pass (augment.py); far above TID_DROP's
 
 # torch-native state_dict parameter order (probed from the reference instance)
 PARAM_ORDER = [

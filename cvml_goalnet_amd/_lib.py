@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GOALNET_LIB_PATH") or os.path.join(_HERE, "libgoalnet_hip.so")   # override: A/B builds of the kernels
@@ -34,6 +34,18 @@ class RowCopyIndexed(ctypes.Structure):
 class AdamRange(ctypes.Structure):
     """goalnet_adam_range (include/goalnet_hip.h)"""
     _fields_ = [("begin", c_int64), ("count", c_int64), ("skipped", c_int64)]
+
+
+class OptimRange(ctypes.Structure):
+    """goalnet_optim_range (include/goalnet_optim.h)"""
+    _fields_ = [("begin", c_int64), ("count", c_int64), ("skipped", c_int64), ("decay", c_int32), ("pad", c_int32)]
+
+
+class OptimOpts(ctypes.Structure):
+    """goalnet_optim_opts (include/goalnet_optim.h)"""
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
+                ("max_norm", c_double), ("min_lr", c_double), ("gamma", c_double), ("warmup", c_int64), ("total", c_int64),
+                ("period", c_int64), ("decoupled", c_int32), ("schedule", c_int32)]
 
 
 # name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_hip.h
@@ -198,6 +210,17 @@ PLAN_WORDS = 8            # GOALNET_PLAN_WORDS
 MAX_SHIFT = 32767         # GOALNET_MAX_SHIFT
 ROWCOPY_MAX = 4           # GOALNET_ROWCOPY_MAX
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_optim.h, the fourth public header (weight decay,
+# gradient-norm clipping and learning-rate schedules on the fused step): additions, the tables above stay as they are
+OPTIM_PROTOTYPES = {
+    "goalnet_grad_sumsq_ws_bytes": (c_size_t, [ctypes.POINTER(OptimRange), c_int]),
+    "goalnet_grad_sumsq": (c_int, [P, ctypes.POINTER(OptimRange), c_int, P, P, c_size_t, P]),
+    "goalnet_optim_step_dev_ranges": (c_int, [P, P, P, P, ctypes.POINTER(OptimRange), c_int, ctypes.POINTER(OptimOpts), P, c_float, P,
+                                              P, c_int64, c_int64, c_int, P, P]),
+    "goalnet_optim_lr": (c_int, [ctypes.POINTER(OptimOpts), P, P, P]),
+}
+SCHEDULES = {"constant": 0, "cosine": 1, "step": 2}       # GOALNET_SCHED_* (include/goalnet_optim.h)
+
 _lib = None
 
 
@@ -215,7 +238,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items()):
+    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

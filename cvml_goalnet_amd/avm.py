@@ -217,6 +217,38 @@ def epi_fuse_dw_adam(n, *, plain, synced, precision, train_w5, shadowed, inspect
     return forced is True or n >= EPI_FUSE_MIN_ROWS
 
 
+def optim_step_path(optim, *, sharded):
+    """Does this optimizer step run under options (optim.OptimOptions)? None or trivial options: False — today's plan,
+    launch for launch (early Adam, epilogue-fused linear5 update, the arena passes). Otherwise True: no early Adam and no fused
+    epilogue — clipping needs the whole norm before any update and both shortcuts hard-code plain Adam — but, after backward, the
+    gradient exchange and the fp16 finite check, ops.grad_sumsq (clipping only) and ONE ops.optim_step_dev_ranges over optim_ranges().
+    `sharded` (ddp.GradSync(shard_linear5=True)) refuses: a rank holds only its slice of that gradient. Pure: the host tests call it."""
+    if optim is None or optim.trivial:
+        return False
+    if sharded:
+        raise GoalnetError("optimizer options (weight decay, clipping, schedules) are not built for ddp.GradSync(shard_linear5=True): "
+                           "a rank holds only its slice of linear5.weight's gradient; use a plain GradSync")
+    return True
+
+
+def optim_ranges(specs, frozen, skipped, optim):
+    """[(begin, count, skipped, decay)]: trainable_ranges() split further wherever the decay flag changes (optim.decays(name): weight
+    decay is on and no `no_decay` substring matches). Neighbours merge, slot padding included (zero in all four arenas, and zero under
+    decay), while they share the count of sat-out steps AND the flag. Pure: the host tests call it."""
+    out, slot_end = [], None
+    for s in sorted(specs, key=lambda s: s.offset):
+        if s.name in frozen:
+            slot_end = None
+            continue
+        k, d = int(skipped.get(s.name, 0)), bool(optim.decays(s.name))
+        if out and slot_end == s.offset and out[-1][2] == k and out[-1][3] == d:
+            out[-1] = (out[-1][0], s.offset + s.numel - out[-1][0], k, d)
+        else:
+            out.append((s.offset, s.numel, k, d))
+        slot_end = s.offset + (s.numel + _ALIGN - 1) // _ALIGN * _ALIGN
+    return out
+
+
 class AVM(_LazyFlags, nn.Module):
     def __init__(self, audio_included, device=None, seed: Optional[int] = None, precision: str = "fp32", head: str = "regression",
                  num_classes: int = 5):
@@ -1420,8 +1452,11 @@ class AVM(_LazyFlags, nn.Module):
     # device-resident fused train step: forward, broadcast MSE, backward, Adam
     # ------------------------------------------------------------------------------------------
     def train_step(self, audio, visual, labels, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, _loop_tick=(0, 0), _scatter=None, *,
-                   loss="mse_bcast", loss_param=None, weights=None):
+                   loss="mse_bcast", loss_param=None, weights=None, optim=None):
         """main.py:187-193 on GPU tensors. Returns (loss (1,), pred (N,)) as GPU tensors, no host sync.
+        `optim` (EXTENSION): optim.OptimOptions — weight decay, gradient-norm clipping, a learning-rate schedule on
+        `lr`. None or trivial options: exactly the step without the argument. Otherwise the update is one launch after backward
+        (optim_step_path): no early Adam, no update in linear5's weight-gradient epilogue.
         `loss` (EXTENSION): "mse_bcast" is the reference's nn.MSELoss with its (n,1) x (n,) broadcast; "mse", "l1",
         "smooth_l1" (loss_param = beta, default 1) are the per-frame losses mean(w_i l_i) with optional fp32 `weights` (N,); "rank" is the
         pairwise logistic loss over the pairs with y_i > y_j. Up to 16 frames the loss rides in the fused MLP launch, above it is
@@ -1434,6 +1469,7 @@ class AVM(_LazyFlags, nn.Module):
         grad_of("visbl.linear5.weight") returns whatever an earlier backward left there. keep_ctx = True or epi_fuse = False keep it."""
         loss_kind = loss
         ops.loss_spec(loss_kind, loss_param, weights is not None, self.head)       # ValueError before anything is launched
+        opt_on = optim_step_path(optim, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
         n0 = visual.shape[0]
         if weights is not None:
             if not (torch.is_tensor(weights) and weights.dtype == F32 and weights.numel() == n0):
@@ -1488,7 +1524,9 @@ class AVM(_LazyFlags, nn.Module):
         fuse5 = epi_fuse_dw_adam(n, plain=plain, synced=sync is not None, precision=self.precision,
                                  train_w5="visbl.linear5.weight" not in frozen, shadowed=self._w5b is not None, inspected=self.keep_ctx,
                                  forced=self.epi_fuse, pieces=epi_fuse_pieces(os.environ.get("GOALNET_F32_EPI_FUSE")))
-        early = early and not fuse5
+        if opt_on:
+            fuse5 = False                                 # both shortcuts hard-code plain Adam, and clipping needs the whole norm first
+        early = early and not fuse5 and not opt_on
         # (small steps: the same update as a background pass on a third stream was measured slower at every width)
         done_early = []
 
@@ -1534,7 +1572,7 @@ class AVM(_LazyFlags, nn.Module):
                 for lo, hi in self._exact_runs(names):
                     ops.grad_finite_check(self._garena[lo:hi], self._state[0], self._guard[0], self._guard[1])
             guard = self._guard[0]
-        self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early)
+        self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early, optim=optim if opt_on else None)
         if _scatter is not None:
             ops.rows_scatter_tick(_scatter(loss, out), self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], bad_step=guard)
         elif guard is not None:
@@ -1609,11 +1647,12 @@ class AVM(_LazyFlags, nn.Module):
         else:
             ops.adam_step_dev(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], grad_scale, step_bias=1)
 
-    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, _tick=True, _guard=None, _done=()):
+    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, _tick=True, _guard=None, _done=(), optim=None):
         """torch.optim.Adam defaults over the whole arena in one launch (main.py:70, 193). The step count is the device
         counter state[0] (= completed steps) + 1, so the same captured launch serves every step. With a sharded
         linear5.weight (ddp.py) the pass covers this rank's slice only — three launches — and the optimizer state exists
-        only for what the rank owns."""
+        only for what the rank owns. `optim` (optim.OptimOptions): non-trivial options run _optim_step instead."""
+        opt_on = optim_step_path(optim, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
         frozen = self._bwd_frozen
         self._check_freeze(frozen)
         if self.precision == "fp16":
@@ -1622,6 +1661,9 @@ class AVM(_LazyFlags, nn.Module):
                 self._fp16_frozen = frozen
             elif self._fp16_frozen != frozen:
                 raise GoalnetError("precision='fp16': the set of frozen tensors may not change after the first optimizer step")
+        if opt_on:
+            assert not _done
+            return self._optim_step(lr, betas, eps, grad_scale, optim, frozen, _tick, _guard)
         segs = self._adam_state()
         self._adam_t += 1
         if not self._plain_step(frozen):
@@ -1659,6 +1701,51 @@ class AVM(_LazyFlags, nn.Module):
             self.grad_sync.after_adam(self, self._w5b if shadow_ok else None)
         if _tick:
             ops.counter_add(self._state[0], 1)
+
+    def _optim_step(self, lr, betas, eps, grad_scale, optim, frozen, _tick, _guard):
+        """adam_step under non-trivial options: the squared norm of the trainable gradients (clipping only; after the gradient exchange,
+        so grad_scale carries 1 / world) and ONE launch over the trainable ranges, split where the decay flag changes. The learning
+        rate is the schedule's at the device step counter; 16-bit copy and fp16 guard pass through as in _adam_piece."""
+        ranges = optim_ranges(self._specs, frozen, self._sat_out, optim)
+        if len(ranges) > ops.ADAM_RANGES_MAX:
+            raise GoalnetError(f"{len(ranges)} trainable ranges (split by weight decay): the fused step takes {ops.ADAM_RANGES_MAX}")
+        segs = self._adam_state()
+        assert segs == [(0, self._arena_numel)]
+        self._adam_t += 1
+        s5 = self.spec("visbl.linear5.weight")
+        shadow = self._w5b if (s5.name not in frozen and self._w5b is not None and self._w5b_version == self._w5_version()) else None
+        if ranges:
+            sumsq = ops.grad_sumsq(self._garena, ranges) if optim.max_grad_norm is not None else None
+            ops.optim_step_dev_ranges(self._arena, self._garena, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps, optim,
+                                      self._state[0], grad_scale, sumsq=sumsq, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
+        self._count_sat_out(frozen)
+        if _tick:
+            ops.counter_add(self._state[0], 1)
+
+    def grad_norm(self) -> torch.Tensor:
+        """(1,) float64 on the device, no sync: the L2 norm of the gradients of the tensors that trained in the last backward, as the
+        gradient arena holds them (ops.grad_sumsq over the trainable ranges), divided by the loss scale an fp16 train_step left in
+        the arena. What max_grad_norm is compared with. After a step that updated linear5.weight in its weight-gradient epilogue
+        (train_step's docstring) that tensor's slot holds an earlier backward's gradient."""
+        if self._garena is None:
+            raise RuntimeError("grad_norm() before any backward: there are no gradients")
+        ranges = [(b, c, k, False) for b, c, k in trainable_ranges(self._specs, self._bwd_frozen, self._sat_out)]
+        if not ranges:
+            return torch.zeros(1, dtype=torch.float64, device=self._device)
+        if len(ranges) > ops.ADAM_RANGES_MAX:
+            raise GoalnetError(f"{len(ranges)} trainable ranges: one launch takes {ops.ADAM_RANGES_MAX}")
+        norm = ops.grad_sumsq(self._garena, ranges).sqrt_()
+        return norm / self._arena_grad_scale if self._arena_grad_scale != 1.0 else norm
+
+    def current_lr(self, lr=1e-3, optim=None) -> float:
+        """the learning rate the next optimizer step runs at under `optim` (optim.OptimOptions; None: `lr`), evaluated by the device from
+        its step counter (ops.optim_lr). One read-back."""
+        if optim is None:
+            return float(lr)
+        self._require_device()
+        if self._state is None:
+            self._make_state()
+        return float(ops.optim_lr(lr, optim, self._state[0]).item())
 
     def make_optimizer(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         """`optim.Adam(model.parameters(), lr)` (main.py:70) as one fused pass over the arena: cvml_goalnet_amd.optim.Adam"""

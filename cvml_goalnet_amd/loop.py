@@ -22,6 +22,14 @@ The first sub-batch of each size runs eagerly (it is a real step — it also all
 cached operand buffers); the graph is captured at the second occurrence. Capturing executes nothing, so the
 sequence of optimizer steps is exactly the reference's.
 
+The learning rate is a launch argument, so a captured graph bakes in the `lr` it was captured with and the graph key does not carry
+it: changing `trainer.lr` after a size's first capture has no effect on that size's replays. A rate that changes over the run is a
+schedule: `optim=OptimOptions(schedule=..., warmup_steps=...)` is evaluated on the device from the step counter,
+inside every replay, with `lr` as its base rate.
+
+EXTENSION (off by default): `optim=OptimOptions(...)` — weight decay, gradient-norm clipping and learning-rate
+schedules on every sub-batch's optimizer step (`AVM.train_step(optim=)`); the graph key carries `optim.signature()`.
+
 EXTENSION (off by default): `shuffle=True` / `augment={...}` draw a plan per pass on the device — frame order, flip,
 shift, contrast, brightness per frame — and the same graphs gather their sub-batches through it; predictions come back in frame order.
 """
@@ -32,6 +40,7 @@ from typing import Dict, Tuple
 import torch
 
 from . import augment as _augment, ops, synth
+from .optim import OptimOptions
 
 F32 = torch.float32
 
@@ -39,9 +48,15 @@ F32 = torch.float32
 class VideoTrainer:
     def __init__(self, model, subbatch_size: int = 10, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  graphs: bool = True, loss: str = "mse_bcast", loss_param=None, shuffle: bool = False, augment=None,
-                 seed: int = synth.BASE_SEED):
+                 seed: int = synth.BASE_SEED, optim=None):
         if subbatch_size < 1:
             raise ValueError("subbatch_size must be >= 1")
+        if optim is not None and not isinstance(optim, OptimOptions):
+            raise ValueError("optim must be an optim.OptimOptions")
+        # EXTENSION: optimizer options of every sub-batch's step. None / trivial: train_step is called as before.
+        self.optim = None if (optim is None or optim.trivial) else optim
+        self._optim_sig = () if self.optim is None else self.optim.signature()
+        self._okw = {} if self.optim is None else {"optim": self.optim}
         # EXTENSION: a fresh frame order and fresh pixels per pass, drawn on the device into a plan table that the
         # captured graphs read. Off by default: with shuffle=False and no augmentation switched on, _sub_step is today's launches.
         self.augment = _augment.augment_options(augment)        # ValueError: unknown option, value out of range
@@ -58,7 +73,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -117,7 +132,7 @@ class VideoTrainer:
         ops.rows_copy_batch(segs)                                       # frames[a:b], labels[a:b], audios[a:b], weights[a:b]
         # train_step advances all four counters in its last launch: cursor += n, sub-batch index += 1
         if m.head == "classifier":
-            loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1))
+            loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **self._okw)
             pred = ops.argmax_plus1(pred, torch.empty(n, dtype=F32, device=dev))        # main.py:190: argmax + 1 is what gets collected
             # predictions.extend(...), losses.append(...) at the positions the step started from
             ops.rows_copy_batch([(self._pred, pred, n, st[2], -n, False), (self._loss, loss, 1, st[3], -1, False)])
@@ -125,7 +140,7 @@ class VideoTrainer:
         # regression head: that same last launch first writes predictions.extend(...), losses.append(...) at the positions the step
         # started from (main.py:195-196), then moves the counters
         m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1),
-                     _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)], **lkw)
+                     _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)], **lkw, **self._okw)
 
     def _sub_step_planned(self, n: int, vis, lab):
         """_sub_step with the sub-batch taken through the pass plan: frames plan[cursor : cursor + n] in that order, augmented as their
@@ -148,7 +163,7 @@ class VideoTrainer:
             lkw = dict(loss=self.loss, loss_param=self.loss_param, weights=wts)
         ops.rows_copy_indexed(segs, self._plan)
         # the step's last launch moves the counters; the results are then written at the positions the step started from
-        loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **lkw)
+        loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **lkw, **self._okw)
         if m.head == "classifier":
             pred = ops.argmax_plus1(pred, torch.empty(n, dtype=F32, device=dev))        # main.py:190
         ops.rows_copy_indexed([(self._pred, pred, n, st[2], -n, False, True), (self._loss, loss, 1, st[3], -1, False, False)], self._plan)
@@ -179,8 +194,10 @@ class VideoTrainer:
         # The loss is baked in too (its kind and beta are launch arguments, the weights a gathered segment): the key carries it.
         # (shuffle, colour, any-augment): which gather the graph holds; the draws themselves live in the plan table. The tests read
         # k[0] as the size, k[3] as the loss and k[-1] as the mode, so the new field sits in front of the mode.
+        # The optimizer options (weight decay, clip norm, schedule constants) are launch arguments as well: their signature is k[5],
+        # () without options. The schedule itself advances inside replays: it reads the device step counter.
         gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted),
-                (self.shuffle, self._colour, self._augments), m.training)
+                (self.shuffle, self._colour, self._augments), self._optim_sig, m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds

@@ -989,6 +989,69 @@ def adam_step_dev_ranges(p, g, m, v, ranges, lr, beta1, beta2, eps, step, grad_s
           "adam_step_dev_ranges")
 
 
+# ---- optimizer options on the fused step (include/goalnet_optim.h, DESIGN.md §4.14) ----
+def _optim_ranges(who, ranges, n):
+    """[(begin, count, skipped, decay)] -> goalnet_optim_range[]"""
+    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"{who}: 1..{_lib.ADAM_RANGES_MAX} ranges")
+    _req(all(b >= 0 and c > 0 and b + c <= n for b, c, _, _ in ranges), f"{who}: a range leaves the arena")
+    return (_lib.OptimRange * len(ranges))(*[_lib.OptimRange(int(b), int(c), int(k), int(bool(d)), 0) for b, c, k, d in ranges])
+
+
+def _optim_opts(lr, beta1, beta2, eps, optim):
+    """the host structure of one launch: base rate and betas of the call, everything else from the OptimOptions"""
+    return _lib.OptimOpts(float(lr), float(beta1), float(beta2), float(eps), float(optim.weight_decay),
+                          0.0 if optim.max_grad_norm is None else float(optim.max_grad_norm), float(optim.min_lr), float(optim.gamma),
+                          int(optim.warmup_steps), int(optim.total_steps or 0), int(optim.step_period or 0), int(optim.decoupled),
+                          _lib.SCHEDULES[optim.schedule])
+
+
+def grad_sumsq(g, ranges, out=None):
+    """sum of g[i]^2 over `ranges` = [(begin, count, skipped, decay)] of the gradient arena, in fp64, into out (1,) float64: two launches,
+    fixed shares and a fixed order, so the same data gives the same bits"""
+    _chk(g, out)
+    _req(g.dtype == F32 and g.is_contiguous(), "grad_sumsq: g must be a contiguous fp32 arena")
+    arr = _optim_ranges("grad_sumsq", ranges, g.numel())
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=g.device)
+    _req(out.dtype == torch.float64 and out.numel() == 1, "grad_sumsq: out must be one float64")
+    nbytes = lib().goalnet_grad_sumsq_ws_bytes(arr, len(ranges))
+    _req(nbytes > 0, "grad_sumsq: the ranges must be sorted, disjoint and begin at multiples of 4")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=g.device)
+    check(lib().goalnet_grad_sumsq(g.data_ptr(), arr, len(ranges), out.data_ptr(), ws.data_ptr(), nbytes, _s()), "grad_sumsq")
+    return out
+
+
+def optim_step_dev_ranges(p, g, m, v, ranges, lr, beta1, beta2, eps, optim, step, grad_scale=1.0, sumsq=None, shadow=None, shadow_begin=0,
+                          bad_step=None):
+    """adam_step_dev_ranges under `optim` (optim.OptimOptions) over `ranges` = [(begin, count, skipped, decay)] in ONE launch: the rate
+    of the schedule at *step, the clip coefficient from `sumsq` (grad_sumsq; required iff optim.max_grad_norm is set), weight decay
+    on the ranges flagged `decay`. Without any of them it is adam_step_dev_ranges, bit for bit."""
+    _chk(p, g, m, v, shadow, sumsq)
+    n = p.numel()
+    _req(g.numel() == n and m.numel() == n and v.numel() == n, "optim_step_dev_ranges: p, g, m, v must have the same size")
+    arr = _optim_ranges("optim_step_dev_ranges", ranges, n)
+    _req((sumsq is None) == (optim.max_grad_norm is None), "optim_step_dev_ranges: sumsq goes with max_grad_norm, and only with it")
+    _req(sumsq is None or (sumsq.dtype == torch.float64 and sumsq.numel() == 1), "optim_step_dev_ranges: sumsq must be one float64")
+    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
+         "optim_step_dev_ranges: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
+    opts = _optim_opts(lr, beta1, beta2, eps, optim)
+    check(lib().goalnet_optim_step_dev_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), arr, len(ranges), ctypes.byref(opts),
+                                              _ctr(step), grad_scale, _p(sumsq), _p(shadow), int(shadow_begin),
+                                              0 if shadow is None else shadow.numel(), 0 if shadow is None else _f16(shadow),
+                                              0 if bad_step is None else _ctr(bad_step), _s()), "optim_step_dev_ranges")
+
+
+def optim_lr(lr, optim, step, out=None):
+    """the learning rate of the step that starts from *step completed steps, as the device evaluates it, into out (1,) float64"""
+    _chk(out)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=step.device)
+    _req(out.dtype == torch.float64 and out.numel() == 1, "optim_lr: out must be one float64")
+    opts = _optim_opts(lr, 0.9, 0.999, 1e-8, optim)
+    check(lib().goalnet_optim_lr(ctypes.byref(opts), _ctr(step), out.data_ptr(), _s()), "optim_lr")
+    return out
+
+
 def scale_(x, s):
     _chk(x)
     _req(x.dtype == F32 and x.is_contiguous(), "scale_: argument check failed: x.dtype == F32 and x.is_contiguous()")

@@ -10,19 +10,130 @@ autograd leaves their gradients in its gradient arena: `_AVMFunction.backward`);
 the first forward (Lazy parameters). Parameters with `requires_grad=False` are left alone, moments and step count included (pass all
 parameters or only the trainable ones). `zero_grad()` only drops the `.grad` references: the gradient arena is overwritten by every
 backward. State (`exp_avg`, `exp_avg_sq`, step) lives in the model (`AVM._adam_m`, `_adam_v`, the device step counter).
+
+EXTENSION: `OptimOptions` — weight decay (coupled as `torch.optim.Adam(weight_decay=)`, decoupled as
+`torch.optim.AdamW`), clipping by the global gradient norm (`torch.nn.utils.clip_grad_norm_`) and a learning-rate schedule that the
+device evaluates from its step counter — for `AVM.train_step(optim=)`, `AVM.adam_step(optim=)`, `loop.VideoTrainer(optim=)` and the
+drop-in `Adam(weight_decay=, max_grad_norm=, options=)` / `AdamW`. No AMSGrad, no per-tensor rates.
 """
 from __future__ import annotations
+
+import dataclasses
+import math
+from typing import Optional, Tuple
 
 import torch
 
 from .avm import AVM
 
+SCHEDULES = ("constant", "cosine", "step")
+
+
+def _is_int(x):
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+@dataclasses.dataclass(frozen=True)
+class OptimOptions:
+    """What the fused step does beyond torch.optim.Adam's defaults. Everything off by default: `trivial`, and the step is then exactly
+    the one without options.
+      weight_decay, decoupled   g += wd * p before Adam (False: torch.optim.Adam) or p *= 1 - lr_t * wd (True: torch.optim.AdamW)
+      no_decay                  name substrings of the tensors that get no decay, e.g. ("bias", "bnorm")
+      max_grad_norm             None, or the cap on the L2 norm of all trainable gradients (torch.nn.utils.clip_grad_norm_)
+      schedule                  "constant" | "cosine" (total_steps, min_lr) | "step" (step_period, gamma), after `warmup_steps` of
+                                linear warm-up; lr_at() is the closed form, the device evaluates the same from its step counter"""
+    weight_decay: float = 0.0
+    decoupled: bool = False
+    no_decay: Tuple[str, ...] = ()
+    max_grad_norm: Optional[float] = None
+    schedule: str = "constant"
+    warmup_steps: int = 0
+    total_steps: Optional[int] = None
+    min_lr: float = 0.0
+    step_period: Optional[int] = None
+    gamma: float = 0.1
+
+    def __post_init__(self):
+        def real(x):
+            return isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x)
+        if not real(self.weight_decay) or self.weight_decay < 0:
+            raise ValueError(f"weight_decay must be a finite number >= 0, got {self.weight_decay!r}")
+        if isinstance(self.no_decay, str) or not all(isinstance(s, str) and s for s in self.no_decay):
+            raise ValueError("no_decay is a tuple of non-empty name substrings")
+        object.__setattr__(self, "no_decay", tuple(self.no_decay))
+        object.__setattr__(self, "decoupled", bool(self.decoupled))
+        if self.max_grad_norm is not None and (not real(self.max_grad_norm) or self.max_grad_norm <= 0):
+            raise ValueError(f"max_grad_norm must be None or a finite number > 0, got {self.max_grad_norm!r}")
+        if self.schedule not in SCHEDULES:
+            raise ValueError(f"schedule must be one of {SCHEDULES}, got {self.schedule!r}")
+        if not _is_int(self.warmup_steps) or self.warmup_steps < 0:
+            raise ValueError(f"warmup_steps must be an integer >= 0, got {self.warmup_steps!r}")
+        if not real(self.min_lr) or self.min_lr < 0:
+            raise ValueError(f"min_lr must be a finite number >= 0, got {self.min_lr!r}")
+        if self.schedule == "cosine":
+            if not _is_int(self.total_steps) or self.total_steps <= self.warmup_steps:
+                raise ValueError("the cosine schedule needs an integer total_steps > warmup_steps")
+        elif self.total_steps is not None and (not _is_int(self.total_steps) or self.total_steps < 0):
+            raise ValueError(f"total_steps must be None or an integer >= 0, got {self.total_steps!r}")
+        if self.schedule == "step":
+            if not _is_int(self.step_period) or self.step_period < 1:
+                raise ValueError("the step schedule needs an integer step_period >= 1")
+            if not real(self.gamma) or self.gamma <= 0:
+                raise ValueError(f"gamma must be a finite number > 0, got {self.gamma!r}")
+        elif self.step_period is not None and (not _is_int(self.step_period) or self.step_period < 1):
+            raise ValueError(f"step_period must be None or an integer >= 1, got {self.step_period!r}")
+
+    @property
+    def trivial(self) -> bool:
+        """nothing is switched on: the step is the one without options, launch for launch"""
+        return self.weight_decay == 0 and self.max_grad_norm is None and self.schedule == "constant" and self.warmup_steps == 0
+
+    def signature(self) -> tuple:
+        """hashable: everything a captured step bakes in about the options (() when trivial)"""
+        if self.trivial:
+            return ()
+        return (float(self.weight_decay), self.decoupled, self.no_decay, None if self.max_grad_norm is None else float(self.max_grad_norm),
+                self.schedule, self.warmup_steps, self.total_steps, float(self.min_lr), self.step_period, float(self.gamma))
+
+    def decays(self, name: str) -> bool:
+        """weight decay applies to the tensor of this name"""
+        return self.weight_decay > 0 and not any(s in name for s in self.no_decay)
+
+    def lr_at(self, base_lr: float, e: int) -> float:
+        """the learning rate of the step that starts from `e` completed steps (step t = e + 1 runs at the rate after t - 1 scheduler
+        ticks, torch's convention) — the expression of csrc/optim.hip's sched_lr, operation for operation"""
+        lr, w = float(base_lr), self.warmup_steps
+        if e < w:
+            return lr * float(e + 1) / float(w)
+        if self.schedule == "cosine":
+            T, e1 = self.total_steps - w, e - w
+            return self.min_lr + (lr - self.min_lr) * (1.0 + math.cos(math.pi * float(min(e1, T)) / float(T))) / 2.0
+        if self.schedule == "step":
+            return lr * math.pow(self.gamma, float((e - w) // self.step_period))
+        return lr
+
+
+def _options(options, weight_decay, max_grad_norm, decoupled):
+    if options is not None:
+        if not isinstance(options, OptimOptions):
+            raise ValueError("options must be an OptimOptions")
+        if weight_decay is not None or max_grad_norm is not None:
+            raise ValueError("pass weight_decay / max_grad_norm either as keywords or inside options, not both")
+        if options.weight_decay > 0 and options.decoupled != decoupled:
+            raise ValueError(f"options.decoupled must be {decoupled} for this optimizer")
+        return options
+    return OptimOptions(weight_decay=0.0 if weight_decay is None else weight_decay, decoupled=decoupled, max_grad_norm=max_grad_norm)
+
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None):
+    _decoupled = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None, weight_decay=None, max_grad_norm=None,
+                 options: Optional[OptimOptions] = None):
         params = list(params)
         if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameters")
+        self.options = _options(options, weight_decay, max_grad_norm, self._decoupled)       # ValueError before anything is launched
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._model = model
 
@@ -51,10 +162,23 @@ class Adam(torch.optim.Optimizer):
         if {id(p) for p in g["params"]} not in (every, trainable):
             raise RuntimeError("cvml_goalnet_amd.optim.Adam steps ALL parameters of its AVM (model.parameters()), or all that have "
                                "requires_grad=True (filter(lambda p: p.requires_grad, model.parameters()))")
-        m.adam_step(g["lr"], tuple(g["betas"]), g["eps"])
+        m.adam_step(g["lr"], tuple(g["betas"]), g["eps"], optim=None if self.options.trivial else self.options)
         return loss
 
     def zero_grad(self, set_to_none: bool = True):
         for g in self.param_groups:
             for p in g["params"]:
                 p.grad = None
+
+
+class AdamW(Adam):
+    """`torch.optim.AdamW(model.parameters(), lr, weight_decay=0.01)`: Adam with decoupled weight decay, p *= 1 - lr_t * wd before the
+    update, on the same fused pass."""
+    _decoupled = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None, weight_decay=None, max_grad_norm=None,
+                 options: Optional[OptimOptions] = None):
+        if options is None and weight_decay is None:
+            weight_decay = 1e-2                     # torch.optim.AdamW's default
+        super().__init__(params, lr=lr, betas=betas, eps=eps, model=model, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         options=options)

@@ -1100,7 +1100,7 @@ static void launch_bnpool_bwd_v2(int nparts, size_t lds, hipStream_t st, const D
     case 4: GN_BWD2(2, 2); break;  case 5: GN_BWD2(2, 3); break;
     case 6: GN_BWD2(3, 3); break;  case 7: GN_BWD2(3, 4); break;
     case 8: GN_BWD2(4, 4); break;  case 9: GN_BWD2(4, 5); break;
-    case 10: GN_BWD2(5, 5); break; default: GN_BWD2(5, 6); break;
+    case 10: GN_BWD2(5, 5); break; default: GN_BWD2(5, 6); break;   // (5, 6) needs Wc = 161 or 162: unreachable, the LDS limit keeps Wc <= 134
     }
 #undef GN_BWD2
 }

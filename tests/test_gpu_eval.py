@@ -10,6 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _width_classes as WC  # noqa: E402
 import eval_ref  # noqa: E402
 from _golden import Golden  # noqa: E402
 from cvml_goalnet_amd import AVM, ops, synth  # noqa: E402
@@ -240,7 +241,8 @@ def _tied(shape, gen):
 
 
 @pytest.mark.parametrize("c,wc,kind", [(64, 14, "f32"), (256, 37, "f32"), (512, 12, "f32"), (64, 170, "f32"), (64, 200, "f32"),
-                                       (256, 37, "bf16"), (512, 20, "fp16"), (256, 23, "bf16_y16"), (64, 170, "fp16_y16")])
+                                       (256, 37, "bf16"), (512, 20, "fp16"), (256, 23, "bf16_y16"), (64, 170, "fp16_y16"),
+                                       *WC.EVAL_FWD_ROWS])
 def test_pool_bn_eval_fwd_equals_pool_bnstats_fwd(c, wc, kind):
     n, hc = 2, 9
     gen = torch.Generator().manual_seed(c + wc)

@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _width_classes as WC
+
 pytestmark = pytest.mark.gpu
 
 from cvml_goalnet_amd import AVM, ops, synth  # noqa: E402
@@ -104,7 +106,7 @@ def test_conv3x3_fp16_weight_gradient_and_linear_layers(tile, monkeypatch):
             assert torch.equal(d16, dxl.to(H))
 
 
-@pytest.mark.parametrize("n,hc,wc,c", [(3, 9, 11, 64), (2, 13, 13, 256)])
+@pytest.mark.parametrize("n,hc,wc,c", [(3, 9, 11, 64), (2, 13, 13, 256), *WC.H16_ROWS])
 def test_fp16_pool_and_batchnorm_passes_match_the_fp32_kernels_on_the_stored_values(n, hc, wc, c):
     g = torch.Generator().manual_seed(193)
     hp, wp = hc - 2, wc - 2

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import _width_classes as WC  # noqa: E402
 from _decisions import saved_mult_check  # noqa: E402
 from _split_emul import check_rows, ideal_split_product, rows_at_exponents, split_host as _split_host  # noqa: E402
 from cvml_goalnet_amd import ops, synth  # noqa: E402
@@ -67,36 +68,47 @@ def test_layout_converters_exact():
     assert torch.equal(wt.cpu().view(12, 3, 3, 8), want)
 
 
-@pytest.mark.parametrize("n,h,w", [(1, 40, 40), (3, 41, 38), (2, 7, 9), (2, 224, 224), (3, 33, 9)])
-def test_conv1_fwd_and_wgrad(n, h, w, monkeypatch):
+def _nan(*shape):
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+def conv1_case(n, h, w, monkeypatch):
+    """conv1 forward and weight gradient on n frames of h x w against F.conv2d in float64, then bit for bit against the first-generation
+    kernels. Every output buffer starts as NaN: an element nobody wrote fails. Shared with tests/test_gpu_width_classes.py."""
     x = rnd(n, 3, h, w, seed=3, lo=0, hi=1)
     wt = rnd(64, 3, 3, 3, seed=4, lo=-0.2, hi=0.2)       # OIHW
     b = rnd(64, seed=5, lo=-0.2, hi=0.2)
     ref = F.relu(F.conv2d(x.double(), wt.double(), b.double(), stride=3, padding=3))
     ho, wo = ref.shape[2], ref.shape[3]
-    y = torch.empty(n, ho, wo, 64, device=DEV)
+    y = _nan(n, ho, wo, 64)
     w_ohwi = wt.permute(0, 2, 3, 1).contiguous().to(DEV)
     ops.conv1_fwd(x.to(DEV), w_ohwi, b.to(DEV), y, n, h, w)
     close("conv1_fwd", y, nhwc(ref))
+    del ref
     dy = rnd(n, ho, wo, 64, seed=6)
     xd = x.double().requires_grad_(False)
     wd = wt.double().requires_grad_(True)
     bd = b.double().requires_grad_(True)
     out = F.conv2d(xd, wd, bd, stride=3, padding=3)
     out.backward(nchw(dy).double())
-    dw = torch.empty(64, 3, 3, 3, device=DEV)
-    db = torch.empty(64, device=DEV)
+    dw = _nan(64, 3, 3, 3)
+    db = _nan(64)
     ops.conv1_wgrad(x.to(DEV), dy.to(DEV), dw, db, n, h, w)
     close("conv1_wgrad.dw", dw, wd.grad.permute(0, 2, 3, 1), rtol=2e-5)
     close("conv1_wgrad.db", db, bd.grad, rtol=2e-5)
     # the row-staged kernels keep the first generation's order of operations: identical bits
     monkeypatch.setenv("GOALNET_CONV1_V1", "1")
-    y1 = torch.empty_like(y)
+    y1 = _nan(*y.shape)
     ops.conv1_fwd(x.to(DEV), w_ohwi, b.to(DEV), y1, n, h, w)
     assert torch.equal(y, y1)
-    dw1, db1 = torch.empty_like(dw), torch.empty_like(db)
+    dw1, db1 = _nan(*dw.shape), _nan(*db.shape)
     ops.conv1_wgrad(x.to(DEV), dy.to(DEV), dw1, db1, n, h, w)
     assert torch.equal(dw, dw1) and torch.equal(db, db1)
+
+
+@pytest.mark.parametrize("n,h,w", [(1, 40, 40), (3, 41, 38), (2, 7, 9), (2, 224, 224), (3, 33, 9)])
+def test_conv1_fwd_and_wgrad(n, h, w, monkeypatch):
+    conv1_case(n, h, w, monkeypatch)
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout,affine,bias,relu", [
@@ -157,10 +169,10 @@ def test_conv3x3_wgrad(n, h, w, cin, cout, affine, path, monkeypatch):
     close(f"conv3x3_wgrad[{n}x{h}x{w}x{cin}->{cout}]", dw, ref.permute(0, 2, 3, 1), rtol=5e-6)
 
 
-@pytest.mark.parametrize("n,hc,wc,c,parts", [(2, 15, 15, 64, 0), (3, 13, 13, 256, 0), (1, 11, 11, 512, 0), (2, 3, 5, 64, 1024),
-                                              (16, 11, 11, 512, 5), (20, 13, 13, 256, 1024), (3, 15, 13, 64, 12), (2, 76, 9, 64, 37),
-                                              (10, 11, 11, 512, 80)])
-def test_pool_bn_forward_and_backward(n, hc, wc, c, parts):
+def pool_bn_case(n, hc, wc, c, parts):
+    """max-pool + BatchNorm statistics / apply and the fused BatchNorm / pool / ReLU backward on a (n, hc, wc, c) conv output against fp64
+    autograd; parts = 0: one partial row per frame. Every output buffer starts as NaN (argmax bytes: 0xFF, no tap): an element nobody
+    wrote fails. Shared with tests/test_gpu_width_classes.py."""
     parts = parts or ops.stat_parts(n)                # partial rows: one per frame / fewer / several row bands per frame
     z = rnd(n, hc, wc, c, seed=16)
     y = F.relu(z)                                     # conv output after ReLU: many exact zeros (ties)
@@ -181,11 +193,11 @@ def test_pool_bn_forward_and_backward(n, hc, wc, c, parts):
     # ---- device
     hp, wp = hc - 2, wc - 2
     yg = y.to(DEV)
-    p = torch.empty(n, hp, wp, c, device=DEV)
-    idx = torch.empty(n, hp, wp, c, dtype=torch.uint8, device=DEV)
-    partials = torch.empty(parts * 2 * c, dtype=torch.float64, device=DEV)
+    p = _nan(n, hp, wp, c)
+    idx = torch.full((n, hp, wp, c), 0xFF, dtype=torch.uint8, device=DEV)
+    partials = _nan(parts * 2 * c).double()
     ops.pool_bnstats_fwd(yg, p, idx, partials, n, hc, wc, c)
-    st = torch.empty(4, c, device=DEV)
+    st = _nan(4, c)
     rmg, rvg = rm0.to(DEV), rv0.to(DEV)
     ops.bn_finalize(partials, gamma.to(DEV), beta.to(DEV), rmg, rvg, 0.1, 1e-5, n * hp * wp, c, st[0], st[1], st[2], st[3])
     close("maxpool", p, nhwc(pd), rtol=0.0)
@@ -206,15 +218,16 @@ def test_pool_bn_forward_and_backward(n, hc, wc, c, parts):
     close("bn.apply(scale,shift)", bn_out, nhwc(od), rtol=2e-6)
     # ---- backward chain
     dbn = nhwc(G.float()).to(DEV)
+    partials.fill_(float("nan"))
     ops.bn_bwd_reduce(dbn, p, st[0], st[1], partials, n * hp * wp, c)
-    coef3 = torch.empty(3 * c, device=DEV)
-    dgamma = torch.empty(c, device=DEV)
-    dbeta = torch.empty(c, device=DEV)
+    coef3 = _nan(3 * c)
+    dgamma = _nan(c)
+    dbeta = _nan(c)
     ops.bn_bwd_finalize(partials, gamma.to(DEV), st[0], st[1], n * hp * wp, c, dgamma, dbeta, coef3)
-    dy = torch.empty(n, hc, wc, c, device=DEV)
-    dparts = torch.empty(parts * c, dtype=torch.float64, device=DEV)
+    dy = _nan(n, hc, wc, c)
+    dparts = _nan(parts * c).double()
     ops.bnpool_bwd(dbn, p, idx, coef3, dy, dparts, n, hc, wc, c)
-    dbias = torch.empty(c, device=DEV)
+    dbias = _nan(c)
     ops.partials_sum(dparts, parts, c, c, dbias)
     close("bn.dgamma", dgamma, gd.grad, rtol=5e-6)
     close("bn.dbeta", dbeta, bd.grad, rtol=5e-6)
@@ -222,6 +235,13 @@ def test_pool_bn_forward_and_backward(n, hc, wc, c, parts):
     # sum(dz) cancels (BatchNorm backward sums to ~0 per channel): tolerance relative to |dz| * sqrt(count)
     close("block.dbias", dbias, zd.grad.sum(dim=(0, 2, 3)), rtol=0.0,
           atol=3e-6 * zd.grad.abs().max().item() * (n * hc * wc) ** 0.5)
+
+
+@pytest.mark.parametrize("n,hc,wc,c,parts", [(2, 15, 15, 64, 0), (3, 13, 13, 256, 0), (1, 11, 11, 512, 0), (2, 3, 5, 64, 1024),
+                                              (16, 11, 11, 512, 5), (20, 13, 13, 256, 1024), (3, 15, 13, 64, 12), (2, 76, 9, 64, 37),
+                                              (10, 11, 11, 512, 80)])
+def test_pool_bn_forward_and_backward(n, hc, wc, c, parts):
+    pool_bn_case(n, hc, wc, c, parts)
 
 
 @pytest.mark.parametrize("m,k,j,affine,mask,ldextra", [
@@ -646,7 +666,7 @@ def test_bf16_gradient_outputs_equal_the_fp32_outputs_rounded_once(tile, monkeyp
         ops.linear_bwd_dx_bf16_o16(dy, w, torch.empty(m, k, dtype=torch.bfloat16, device=DEV))
 
 
-@pytest.mark.parametrize("n,hc,wc,c", [(3, 9, 11, 64), (2, 13, 13, 256)])
+@pytest.mark.parametrize("n,hc,wc,c", [(3, 9, 11, 64), (2, 13, 13, 256), *WC.H16_ROWS])
 def test_batchnorm_backward_passes_with_bf16_gradient_input(n, hc, wc, c):
     """bn_bwd_reduce and the fused BN/pool/ReLU backward fed a bf16 dz must equal, bit for bit, the same kernels fed
     those values as fp32."""
@@ -682,7 +702,7 @@ def test_batchnorm_backward_passes_with_bf16_gradient_input(n, hc, wc, c):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("n,hc,wc,c,kind", [(3, 13, 13, 256, "relu"), (2, 11, 11, 512, "signed"), (2, 9, 40, 64, "special"),
-                                            (1, 76, 74, 64, "relu"), (4, 3, 3, 32, "signed")])
+                                            (1, 76, 74, 64, "relu"), (4, 3, 3, 32, "signed"), *WC.K16_ROWS])
 def test_integer_key_pool_is_bit_identical_to_the_compare_and_select_kernel(n, hc, wc, c, kind, dtype, monkeypatch):
     """16-bit conv output -> 16-bit pooled activation: the integer-key kernel (max over (value << 16 | 8 - tap) words; windows
     holding a negative value, -0.0 or a NaN take its exact path) against v2's float compare-and-select on the same input:
@@ -719,7 +739,7 @@ def test_integer_key_pool_is_bit_identical_to_the_compare_and_select_kernel(n, h
         assert torch.equal(out["v2"][2], out["k16"][2]), "fp64 partial rows differ"
 
 
-@pytest.mark.parametrize("n,hc,wc,c", [(3, 9, 11, 64), (2, 13, 13, 256), (2, 40, 37, 32)])
+@pytest.mark.parametrize("n,hc,wc,c", [(3, 9, 11, 64), (2, 13, 13, 256), (2, 40, 37, 32), *WC.H16_ROWS])
 def test_bf16_pooled_activation_variants_match_the_fp32_kernels_on_the_stored_values(n, hc, wc, c):
     """precision="bf16" stores the pooled activation p of blocks 2 and 3 as bf16. The p16 pool kernel must store exactly
     bf16(max), keep the argmax, and take its statistics from the stored values; every consumer fed the bf16 tensor must

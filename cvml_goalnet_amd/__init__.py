@@ -5,18 +5,19 @@ surface. See DESIGN.md / INTEGRATION.md.
     from cvml_goalnet_amd import AVM               # drop-in for /root/reference/utils.py:229 `AVM`
     from cvml_goalnet_amd import VideoSummarizer   # /root/reference/main.py:315-345 (`--infer`) on a video resident on the GPU
     from cvml_goalnet_amd import epoch_plan, gather_augmented  # shuffled / augmented passes drawn on the GPU (extension)
+    from cvml_goalnet_amd import EmaOptions        # a weight average behind the fused step; exact save / resume (extension)
     from cvml_goalnet_amd import TemporalSegmenter # KTS change points for a video outside the dataset (extension, parity unpinned)
 """
 from . import synth  # noqa: F401
 from ._lib import GoalnetError, LIB_PATH  # noqa: F401
 from .avm import AVM  # noqa: F401
 from . import optim  # noqa: F401
-from .optim import OptimOptions  # noqa: F401
+from .optim import EmaOptions, OptimOptions  # noqa: F401
 from .summarize import VideoSummarizer, VideoSummary  # noqa: F401
 from . import groundtruth  # noqa: F401
 from .segment import Segmentation, TemporalSegmenter  # noqa: F401
 from .rankcorr import HumanConsistency, RankCorrelation, RankEvaluator, rank_correlation  # noqa: F401
 from .augment import epoch_plan, gather_augmented  # noqa: F401
 
-__all__ = ["epoch_plan", "gather_augmented","AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "OptimOptions","VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
+__all__ = ["epoch_plan", "gather_augmented","AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "OptimOptions", "EmaOptions","VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
            "Segmentation", "RankEvaluator", "RankCorrelation", "HumanConsistency", "rank_correlation"]

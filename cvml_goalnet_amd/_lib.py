@@ -48,6 +48,11 @@ class OptimOpts(ctypes.Structure):
                 ("period", c_int64), ("decoupled", c_int32), ("schedule", c_int32)]
 
 
+class EmaOpts(ctypes.Structure):
+    """goalnet_ema_opts (include/goalnet_ema.h)"""
+    _fields_ = [("decay", c_double), ("every", c_int64), ("start_step", c_int64), ("warmup", c_int32), ("pad", c_int32)]
+
+
 # name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_hip.h
 PROTOTYPES = {
     "goalnet_abi_version": (c_int, []),
@@ -221,6 +226,13 @@ OPTIM_PROTOTYPES = {
 }
 SCHEDULES = {"constant": 0, "cosine": 1, "step": 2}       # GOALNET_SCHED_* (include/goalnet_optim.h)
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_ema.h, the fifth public header (the weight
+# average behind the fused step and the exchange of two arenas): additions, the tables above stay as they are
+EMA_PROTOTYPES = {
+    "goalnet_ema_update_dev_ranges": (c_int, [P, P, ctypes.POINTER(AdamRange), c_int, ctypes.POINTER(EmaOpts), P, c_int64, P, P]),
+    "goalnet_swap_ranges": (c_int, [P, P, ctypes.POINTER(AdamRange), c_int, P]),
+}
+
 _lib = None
 
 
@@ -238,7 +250,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items()):
+    for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
+                              *EMA_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -27,6 +27,7 @@ the broadcast MSE, backward, (optional) gradient all-reduce and the fused Adam w
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import List, Optional
@@ -231,6 +232,25 @@ def optim_step_path(optim, *, sharded):
     return True
 
 
+def ema_step_path(ema, *, sharded):
+    """Does this optimizer step move a weight average (optim.EmaOptions)? None: False — no arena, no launch. Otherwise
+    True: ONE ops.ema_update_dev_ranges over trainable_ranges() behind every update of the step, in front of the launch that advances
+    the counters. The average observes: it switches off neither the early Adam nor the epilogue-fused update. `sharded`
+    (ddp.GradSync(shard_linear5=True)) refuses: a rank's fp32 master of the foreign slices of linear5.weight is stale between steps.
+    Pure: the host tests call it."""
+    if ema is None:
+        return False
+    if not (hasattr(ema, "weight_at") and hasattr(ema, "signature")):
+        raise ValueError("ema must be an optim.EmaOptions")
+    if sharded:
+        raise GoalnetError("a weight average (ema=) is not built for ddp.GradSync(shard_linear5=True): a rank holds only its slice of "
+                           "linear5.weight's up-to-date master; use a plain GradSync")
+    return True
+
+
+STATE_FORMAT = 1               # AVM.training_state()["format"]
+
+
 def optim_ranges(specs, frozen, skipped, optim):
     """[(begin, count, skipped, decay)]: trainable_ranges() split further wherever the decay flag changes (optim.decays(name): weight
     decay is on and no `no_decay` substring matches). Neighbours merge, slot padding included (zero in all four arenas, and zero under
@@ -330,6 +350,10 @@ class AVM(_LazyFlags, nn.Module):
         self._arena_grad_scale = 1.0       # the gradient arena currently holds this factor x gradient (fp16 train_step)
         self._w5b, self._w5b_version = None, None      # bf16 shadow of visbl.linear5.weight and the version stamps it matches
         self._load_count = 0                           # bumped by load_state_dict (its layout kernels write the arena directly)
+        # the weight average: a third flat fp32 arena in the parameter arena's layout, allocated by the first step
+        # that is given ema=; _averaged: inside `with model.averaged()` the two arenas are exchanged
+        self._ema = None
+        self._averaged = False
         self._state = None             # int64[4] device counters: adam step, dropout draw, frame cursor, sub-batch index
         self._materialized = False
         self.grad_sync = None          # optional ddp.GradSync: gradient exchange between backward and Adam
@@ -608,6 +632,8 @@ class AVM(_LazyFlags, nn.Module):
             raise RuntimeError(f"visbl.linear5.weight has shape {tuple(w5.shape)}, expected (512, 512*H3*W3)")
         hw3 = w5.shape[1] // 512
         l2 = state_dict["audbl.linear3.weight"].shape[1] // 128 if self.audio_included else 0
+        if self._averaged:
+            raise GoalnetError("load_state_dict() inside `with model.averaged()`: the arena holds the averaged weights there")
         self._load_count += 1
         self._materialize(hw3, l2, init=False)
         if self.grad_sync is not None:
@@ -639,6 +665,10 @@ class AVM(_LazyFlags, nn.Module):
                     ops.transpose_inner(t, flat, s.shape[0], s.shape[1], s.shape[2])  # [512][C][HW] -> [512][HW][C]
                 else:
                     flat.copy_(t)
+        if self._ema is not None:
+            # weights from a file: the average restarts from them — in place, captured graphs hold the arena's address
+            # (load_training_state puts the saved average back afterwards)
+            self._ema.copy_(self._arena)
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
     # ------------------------------------------------------------------------------------------
@@ -1156,6 +1186,7 @@ class AVM(_LazyFlags, nn.Module):
         need_aud = need_aud and self.audio_included
         train = frozenset()
         if params:
+            self._refuse_averaged("a parameter backward")
             frozen = self._frozen_names() if frozen is None else frozenset(frozen)
             self._check_freeze(frozen)
             train = frozenset(s.name for s in self._specs) - frozen
@@ -1452,11 +1483,14 @@ class AVM(_LazyFlags, nn.Module):
     # device-resident fused train step: forward, broadcast MSE, backward, Adam
     # ------------------------------------------------------------------------------------------
     def train_step(self, audio, visual, labels, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, _loop_tick=(0, 0), _scatter=None, *,
-                   loss="mse_bcast", loss_param=None, weights=None, optim=None):
+                   loss="mse_bcast", loss_param=None, weights=None, optim=None, ema=None):
         """main.py:187-193 on GPU tensors. Returns (loss (1,), pred (N,)) as GPU tensors, no host sync.
         `optim` (EXTENSION): optim.OptimOptions — weight decay, gradient-norm clipping, a learning-rate schedule on
         `lr`. None or trivial options: exactly the step without the argument. Otherwise the update is one launch after backward
         (optim_step_path): no early Adam, no update in linear5's weight-gradient epilogue.
+        `ema` (EXTENSION): optim.EmaOptions — the average of the weights in the arena `_ema` (ema_of, averaged()) takes
+        this step in: one launch over the trainable ranges behind every update of the step, in front of the counters' launch. None:
+        exactly the step without the argument. The average observes: early Adam and the epilogue-fused update run as without it.
         `loss` (EXTENSION): "mse_bcast" is the reference's nn.MSELoss with its (n,1) x (n,) broadcast; "mse", "l1",
         "smooth_l1" (loss_param = beta, default 1) are the per-frame losses mean(w_i l_i) with optional fp32 `weights` (N,); "rank" is the
         pairwise logistic loss over the pairs with y_i > y_j. Up to 16 frames the loss rides in the fused MLP launch, above it is
@@ -1470,6 +1504,8 @@ class AVM(_LazyFlags, nn.Module):
         loss_kind = loss
         ops.loss_spec(loss_kind, loss_param, weights is not None, self.head)       # ValueError before anything is launched
         opt_on = optim_step_path(optim, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
+        ema_on = ema_step_path(ema, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
+        self._refuse_averaged("train_step")
         n0 = visual.shape[0]
         if weights is not None:
             if not (torch.is_tensor(weights) and weights.dtype == F32 and weights.numel() == n0):
@@ -1490,6 +1526,8 @@ class AVM(_LazyFlags, nn.Module):
         out, ctx = self.forward_device(audio, visual, save=True, fused_loss=fused_loss, caller_ticks=True,
                                        fused_loss_kind=None if loss_kind == "mse_bcast" else (loss_kind, loss_param, weights))
         n = out.shape[0]
+        if ema_on:
+            self._ensure_ema()                            # the first step: the average starts from the weights BEFORE any update
         if ctx["loss_done"]:
             pass
         elif loss_kind != "mse_bcast":
@@ -1572,7 +1610,9 @@ class AVM(_LazyFlags, nn.Module):
                 for lo, hi in self._exact_runs(names):
                     ops.grad_finite_check(self._garena[lo:hi], self._state[0], self._guard[0], self._guard[1])
             guard = self._guard[0]
-        self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early, optim=optim if opt_on else None)
+        # (the early Adam ran on the side stream: backward_device's last act joins it into this stream, so the average, issued by
+        # adam_step behind its own launches, reads every updated weight)
+        self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early, optim=optim if opt_on else None, ema=ema)
         if _scatter is not None:
             ops.rows_scatter_tick(_scatter(loss, out), self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], bad_step=guard)
         elif guard is not None:
@@ -1647,12 +1687,18 @@ class AVM(_LazyFlags, nn.Module):
         else:
             ops.adam_step_dev(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], grad_scale, step_bias=1)
 
-    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, _tick=True, _guard=None, _done=(), optim=None):
+    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, _tick=True, _guard=None, _done=(), optim=None, ema=None):
         """torch.optim.Adam defaults over the whole arena in one launch (main.py:70, 193). The step count is the device
         counter state[0] (= completed steps) + 1, so the same captured launch serves every step. With a sharded
         linear5.weight (ddp.py) the pass covers this rank's slice only — three launches — and the optimizer state exists
-        only for what the rank owns. `optim` (optim.OptimOptions): non-trivial options run _optim_step instead."""
+        only for what the rank owns. `optim` (optim.OptimOptions): non-trivial options run _optim_step instead.
+        `ema` (optim.EmaOptions): behind the update, and in front of the launch that advances the step counter, one
+        launch folds the updated weights into the average (_ema_update)."""
         opt_on = optim_step_path(optim, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
+        ema_on = ema_step_path(ema, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
+        self._refuse_averaged("adam_step")
+        if ema_on:
+            self._ensure_ema()                            # the first step: the average starts from the weights BEFORE the update
         frozen = self._bwd_frozen
         self._check_freeze(frozen)
         if self.precision == "fp16":
@@ -1663,7 +1709,7 @@ class AVM(_LazyFlags, nn.Module):
                 raise GoalnetError("precision='fp16': the set of frozen tensors may not change after the first optimizer step")
         if opt_on:
             assert not _done
-            return self._optim_step(lr, betas, eps, grad_scale, optim, frozen, _tick, _guard)
+            return self._optim_step(lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema if ema_on else None)
         segs = self._adam_state()
         self._adam_t += 1
         if not self._plain_step(frozen):
@@ -1679,6 +1725,8 @@ class AVM(_LazyFlags, nn.Module):
                 ops.adam_step_dev_ranges(self._arena, self._garena, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps,
                                          self._state[0], grad_scale, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
             self._count_sat_out(frozen)
+            if ema_on:
+                self._ema_update(ema, frozen, _guard)
             if _tick:
                 ops.counter_add(self._state[0], 1)
             return
@@ -1699,10 +1747,12 @@ class AVM(_LazyFlags, nn.Module):
         if len(segs) > 1:
             shadow_ok = self._w5b is not None and self._w5b_version == self._w5_version()
             self.grad_sync.after_adam(self, self._w5b if shadow_ok else None)
+        if ema_on:
+            self._ema_update(ema, frozen, _guard)
         if _tick:
             ops.counter_add(self._state[0], 1)
 
-    def _optim_step(self, lr, betas, eps, grad_scale, optim, frozen, _tick, _guard):
+    def _optim_step(self, lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema=None):
         """adam_step under non-trivial options: the squared norm of the trainable gradients (clipping only; after the gradient exchange,
         so grad_scale carries 1 / world) and ONE launch over the trainable ranges, split where the decay flag changes. The learning
         rate is the schedule's at the device step counter; 16-bit copy and fp16 guard pass through as in _adam_piece."""
@@ -1719,8 +1769,162 @@ class AVM(_LazyFlags, nn.Module):
             ops.optim_step_dev_ranges(self._arena, self._garena, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps, optim,
                                       self._state[0], grad_scale, sumsq=sumsq, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
         self._count_sat_out(frozen)
+        if ema is not None:
+            self._ema_update(ema, frozen, _guard)
         if _tick:
             ops.counter_add(self._state[0], 1)
+
+    # ------------------------------------------------------------------------------------------
+    # the weight average
+    # ------------------------------------------------------------------------------------------
+    def _ensure_ema(self):
+        """the average's arena: allocated on first use — in front of that step's first update — as a copy of the WHOLE parameter
+        arena, slot padding included, so frozen tensors' averages equal their weights from the start"""
+        if self._ema is None:
+            self._ema = self._arena.clone()
+        return self._ema
+
+    def _ema_update(self, ema, frozen, guard):
+        """ONE launch over the trainable ranges (frozen tensors are not in them: their average stays equal to the weight, which does not
+        move), issued on the current stream behind every update of this optimizer step and in front of the launch that advances the
+        step counter: t = *step + 1 is the step that has just been applied. `guard` (fp16): a step whose Adam was skipped leaves the
+        average alone."""
+        ranges = trainable_ranges(self._specs, frozen, {})
+        if not ranges:
+            return
+        if len(ranges) > ops.ADAM_RANGES_MAX:
+            raise GoalnetError(f"{len(ranges)} trainable ranges: the weight average takes {ops.ADAM_RANGES_MAX}")
+        ops.ema_update_dev_ranges(self._arena, self._ensure_ema(), ranges, ema, self._state[0], step_bias=1, bad_step=guard)
+
+    def _refuse_averaged(self, what):
+        if self._averaged:
+            raise GoalnetError(f"{what} inside `with model.averaged()`: the arena holds the averaged weights there, and an update "
+                               "would train the average; leave the block first")
+
+    def ema_of(self, name) -> torch.Tensor:
+        """The average of a parameter as a view with the reference's logical shape, like param_of (inside `with model.averaged()`
+        the two are exchanged: ema_of then shows the live weights)."""
+        if self._ema is None:
+            raise GoalnetError("no weight average yet: pass ema=EmaOptions(...) to train_step / adam_step / VideoTrainer first")
+        s = self.spec(name)
+        v = self._view(self._ema, s)
+        return v.reshape(s.shape[0], -1) if s.kind == "lin5" else v
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with model.averaged(): ...` — the parameter arena and the average are exchanged over the whole arena (ops.swap_ranges, one
+        launch) on entry and again on exit, which restores both bit for bit. Inside, forward, eval_video, VideoSummarizer and
+        state_dict() see the averaged weights, so `torch.save(model.state_dict())` there is a checkpoint of the average that the
+        reference's utils.AVM loads. The BatchNorm running buffers are the LIVE ones: they are not averaged (a train-mode forward
+        inside the block moves them as it does outside). Cached operands keyed on the weights' version (the 16-bit copy of
+        linear5.weight) are re-made on both sides. A swap and not a pointer exchange: the nn.Parameter views and captured graphs hold
+        the arena's address. train_step, adam_step, a parameter backward and load_state_dict inside the block raise GoalnetError, as
+        does a nested entry."""
+        if self._averaged:
+            raise GoalnetError("model.averaged() is already active: the block does not nest")
+        if self._ema is None:
+            raise GoalnetError("no weight average yet: pass ema=EmaOptions(...) to train_step / adam_step / VideoTrainer first")
+        if self.grad_sync is not None and getattr(self.grad_sync, "shard_linear5", False):
+            raise GoalnetError("model.averaged() is not built for ddp.GradSync(shard_linear5=True)")
+        whole = [(0, self._arena_numel)]
+        ops.swap_ranges(self._arena, self._ema, whole)
+        self._load_count += 1
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            ops.swap_ranges(self._arena, self._ema, whole)
+            self._load_count += 1
+            self._averaged = False
+
+    # ------------------------------------------------------------------------------------------
+    # exact save / resume (DESIGN.md §4.15)
+    # ------------------------------------------------------------------------------------------
+    def _identity(self):
+        return {"audio_included": bool(self.audio_included), "head": self.head, "num_classes": int(self.num_classes),
+                "precision": self.precision, "hw3": self._hw3, "l2": self._l2}
+
+    def _refuse_sharded_state(self, what):
+        if self.grad_sync is not None and getattr(self.grad_sync, "shard_linear5", False):
+            raise GoalnetError(f"{what} under ddp.GradSync(shard_linear5=True): saving a sharded optimizer state is not built")
+
+    def training_state(self) -> dict:
+        """Everything a run needs to continue as if it had not stopped, as CPU tensors and plain Python values (`torch.save` takes
+        it): "model" = state_dict() — the reference's keys and layouts, so the file doubles as a reference checkpoint —, the Adam
+        moments and the weight average as flat arenas in the arena's own layout, the four device counters and the two fp16 guard
+        words, the host mirrors of the step and dropout counts, dropout seed and mode, the per-tensor counts of sat-out steps and the
+        frozen set the fp16 path pinned, the loss-scale fields, and what identifies the model (load_training_state checks it). One
+        host synchronisation."""
+        self._refuse_sharded_state("training_state()")
+        self._refuse_averaged("training_state()")
+        if not self._materialized:
+            raise RuntimeError("training_state() before the first forward / load_state_dict(): parameters are uninitialised")
+        if self._state is None:
+            self._make_state()
+
+        def cpu(t):
+            return None if t is None else t.detach().cpu().clone()
+        return {
+            "format": STATE_FORMAT,
+            **self._identity(),
+            "model": self.state_dict(),
+            "arena_numel": int(self._arena_numel),
+            "adam_m": cpu(self._adam_m), "adam_v": cpu(self._adam_v), "ema": cpu(self._ema),
+            "counters": cpu(self._state), "guard": cpu(self._guard),
+            "adam_t": int(self._adam_t), "drop_step": int(self._drop_step),
+            "dropout_seed": int(self.dropout_seed), "dropout_mode": self.dropout_mode,
+            "sat_out": {k: int(v) for k, v in self._sat_out.items()},
+            "bwd_frozen": sorted(self._bwd_frozen),
+            "fp16_frozen": None if self._fp16_frozen is None else sorted(self._fp16_frozen),
+            "loss_scale": self._loss_scale, "loss_scale_user": bool(self._loss_scale_user),
+            "loss_scale_backoff": int(self._loss_scale_backoff), "skipped_seen": int(self._skipped_seen),
+        }
+
+    def load_training_state(self, state: dict):
+        """Restore training_state(): the identity fields must match this model (RuntimeError names the first that does not), the model
+        is materialised if needed, and weights, BatchNorm buffers, moments, average, counters, guard words, dropout stream, sat-out
+        counts and loss-scale fields are put back — in place where the tensors exist, since captured graphs hold their addresses.
+        dropout_mode "given" is not restored (its masks are not part of the state): the model's own mode stays."""
+        self._refuse_sharded_state("load_training_state()")
+        self._refuse_averaged("load_training_state()")
+        if not isinstance(state, dict) or state.get("format") != STATE_FORMAT:
+            raise RuntimeError(f"load_training_state: not a training state of format {STATE_FORMAT}")
+        mine = self._identity()
+        for k in ("audio_included", "head", "num_classes", "precision"):
+            if state[k] != mine[k]:
+                raise RuntimeError(f"load_training_state: the state was saved from a model with {k}={state[k]!r}, this one has {k}={mine[k]!r}")
+        for k in ("hw3", "l2"):
+            if self._materialized and state[k] != mine[k]:
+                raise RuntimeError(f"load_training_state: the state was saved from a model with {k}={state[k]!r}, this one has {k}={mine[k]!r}")
+        self.load_state_dict(state["model"])                            # materialises; bumps _load_count
+        if state["arena_numel"] != self._arena_numel:
+            raise RuntimeError(f"load_training_state: arena of {state['arena_numel']} elements, this model's has {self._arena_numel}")
+        if state["adam_m"] is not None:
+            if self._adam_m is None:
+                self._adam_state()                                      # lays the moments out
+            if self._adam_m.numel() != state["adam_m"].numel():
+                raise RuntimeError("load_training_state: the optimizer state was laid out for another sharding")
+            self._adam_m.copy_(state["adam_m"])
+            self._adam_v.copy_(state["adam_v"])
+        elif self._adam_m is not None:
+            self._adam_m.zero_()
+            self._adam_v.zero_()
+        if state["ema"] is not None:
+            self._ensure_ema().copy_(state["ema"])
+        if self._state is None:
+            self._make_state()
+        self._state.copy_(state["counters"])
+        self._guard.copy_(state["guard"])
+        self._adam_t, self._drop_step = int(state["adam_t"]), int(state["drop_step"])
+        self.dropout_seed = int(state["dropout_seed"])
+        if state["dropout_mode"] != "given" and self.dropout_mode != "given":
+            self.dropout_mode = state["dropout_mode"]
+        self._sat_out = {k: int(v) for k, v in state["sat_out"].items()}
+        self._bwd_frozen = frozenset(state["bwd_frozen"])
+        self._fp16_frozen = None if state["fp16_frozen"] is None else frozenset(state["fp16_frozen"])
+        self._loss_scale, self._loss_scale_user = state["loss_scale"], bool(state["loss_scale_user"])
+        self._loss_scale_backoff, self._skipped_seen = int(state["loss_scale_backoff"]), int(state["skipped_seen"])
+        self._load_count += 1
 
     def grad_norm(self) -> torch.Tensor:
         """(1,) float64 on the device, no sync: the L2 norm of the gradients of the tensors that trained in the last backward, as the

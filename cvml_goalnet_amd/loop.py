@@ -30,6 +30,11 @@ inside every replay, with `lr` as its base rate.
 EXTENSION (off by default): `optim=OptimOptions(...)` — weight decay, gradient-norm clipping and learning-rate
 schedules on every sub-batch's optimizer step (`AVM.train_step(optim=)`); the graph key carries `optim.signature()`.
 
+EXTENSION (off by default): `ema=EmaOptions(...)` keeps an exponential moving average of the weights behind every
+sub-batch's optimizer step (`AVM.train_step(ema=)`, one more launch inside the same graphs; the graph key carries `ema.signature()`).
+`state_dict()` / `load_state_dict()` save and restore the run — the model's training state and the trainer's pass index — so that a
+resumed run continues bit for bit.
+
 EXTENSION (off by default): `shuffle=True` / `augment={...}` draw a plan per pass on the device — frame order, flip,
 shift, contrast, brightness per frame — and the same graphs gather their sub-batches through it; predictions come back in frame order.
 """
@@ -40,15 +45,22 @@ from typing import Dict, Tuple
 import torch
 
 from . import augment as _augment, ops, synth
-from .optim import OptimOptions
+from .optim import EmaOptions, OptimOptions
+
+TRAINER_STATE_FORMAT = 1
 
 F32 = torch.float32
+
+
+def _plain(x):
+    """tuples and lists compare alike (a saved state may have passed through a format that knows only lists)"""
+    return [_plain(v) for v in x] if isinstance(x, (tuple, list)) else x
 
 
 class VideoTrainer:
     def __init__(self, model, subbatch_size: int = 10, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  graphs: bool = True, loss: str = "mse_bcast", loss_param=None, shuffle: bool = False, augment=None,
-                 seed: int = synth.BASE_SEED, optim=None):
+                 seed: int = synth.BASE_SEED, optim=None, ema=None):
         if subbatch_size < 1:
             raise ValueError("subbatch_size must be >= 1")
         if optim is not None and not isinstance(optim, OptimOptions):
@@ -57,6 +69,13 @@ class VideoTrainer:
         self.optim = None if (optim is None or optim.trivial) else optim
         self._optim_sig = () if self.optim is None else self.optim.signature()
         self._okw = {} if self.optim is None else {"optim": self.optim}
+        # EXTENSION: the weight average every sub-batch's step is folded into. None: train_step is called as before.
+        if ema is not None and not isinstance(ema, EmaOptions):
+            raise ValueError("ema must be an optim.EmaOptions")
+        self.ema = ema
+        self._ema_sig = () if ema is None else ema.signature()
+        if ema is not None:
+            self._okw = dict(self._okw, ema=ema)
         # EXTENSION: a fresh frame order and fresh pixels per pass, drawn on the device into a plan table that the
         # captured graphs read. Off by default: with shuffle=False and no augmentation switched on, _sub_step is today's launches.
         self.augment = _augment.augment_options(augment)        # ValueError: unknown option, value out of range
@@ -73,7 +92,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, ema signature, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -196,8 +215,10 @@ class VideoTrainer:
         # k[0] as the size, k[3] as the loss and k[-1] as the mode, so the new field sits in front of the mode.
         # The optimizer options (weight decay, clip norm, schedule constants) are launch arguments as well: their signature is k[5],
         # () without options. The schedule itself advances inside replays: it reads the device step counter.
+        # The weight average's constants are launch arguments too, and its arena's address is baked in: its signature is k[6], ()
+        # when off. Which steps copy, average or pass is decided inside replays, from the device step counter.
         gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted),
-                (self.shuffle, self._colour, self._augments), self._optim_sig, m.training)
+                (self.shuffle, self._colour, self._augments), self._optim_sig, self._ema_sig, m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -240,6 +261,33 @@ class VideoTrainer:
         g.replay()
         self._host_bookkeeping_after_replay()
         self.replays += 1
+
+    # ---- exact save / resume --------------------------------------------------------------------------
+    def _signatures(self):
+        return {"loss": (self.loss, self.loss_param), "plan": (self.shuffle, tuple(sorted(self.augment.items()))),
+                "optim": self._optim_sig, "ema": self._ema_sig, "subbatch_size": self.subbatch_size,
+                "step": (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps))}
+
+    def state_dict(self) -> dict:
+        """The run so far, for `torch.save`: the model's training_state() plus the index of the next pass plan, the plan seed and the
+        signatures of loss, shuffle / augment, optimizer options and weight average. Take it between two videos. One host sync."""
+        return {"format": TRAINER_STATE_FORMAT, "model_state": self.model.training_state(), "passes": int(self.passes),
+                "seed": int(self.seed), "signatures": self._signatures()}
+
+    def load_state_dict(self, state: dict):
+        """Continue the run a state_dict() was taken from: the next train_video is the one that run would have made next, bit for bit.
+        ValueError where this trainer's loss, shuffle / augment, optimizer options, weight average, sub-batch size or step constants
+        differ from the saved ones — a changed configuration is not an exact resume —; the model's own mismatches raise
+        RuntimeError (AVM.load_training_state). The captured graphs stay valid: everything is restored in place."""
+        if not isinstance(state, dict) or state.get("format") != TRAINER_STATE_FORMAT:
+            raise ValueError(f"not a VideoTrainer state of format {TRAINER_STATE_FORMAT}")
+        mine = self._signatures()
+        for k, v in state["signatures"].items():
+            if k not in mine or _plain(mine[k]) != _plain(v):
+                raise ValueError(f"this trainer's {k} differs from the saved run's: {mine.get(k)!r} vs {v!r}")
+        self.model.load_training_state(state["model_state"])
+        self.passes = int(state["passes"])
+        self.seed = int(state["seed"])
 
     # ---- validation pass ---------------------------------------------------------------------------------------------
     def eval_video(self, val_audios, val_frames, val_labels, weights=None):

@@ -1052,6 +1052,38 @@ def optim_lr(lr, optim, step, out=None):
     return out
 
 
+# ---- the weight average behind the fused step (include/goalnet_ema.h, DESIGN.md §4.15) ----
+def _plain_ranges(who, ranges, n):
+    """[(begin, count)] or [(begin, count, skipped)] -> goalnet_adam_range[] (the count of sat-out steps is not read)"""
+    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"{who}: 1..{_lib.ADAM_RANGES_MAX} ranges")
+    _req(all(r[0] >= 0 and r[1] > 0 and r[0] + r[1] <= n for r in ranges), f"{who}: a range leaves the arena")
+    return (_lib.AdamRange * len(ranges))(*[_lib.AdamRange(int(r[0]), int(r[1]), 0) for r in ranges])
+
+
+def ema_update_dev_ranges(p, e, ranges, ema, step, step_bias=1, bad_step=None):
+    """the average `e` of the weights `p` over `ranges` in ONE launch, under `ema` (optim.EmaOptions) at the 1-based step count
+    t = *step + step_bias: a copy up to ema.start_step, then every ema.every-th step e += w (p - e) with w = ema.weight_at(t); a step
+    that `bad_step` stamps leaves e alone."""
+    _chk(p, e)
+    n = p.numel()
+    _req(p.dtype == F32 and e.dtype == F32 and p.is_contiguous() and e.is_contiguous() and e.numel() == n,
+         "ema_update_dev_ranges: p and e must be contiguous fp32 arenas of one size")
+    arr = _plain_ranges("ema_update_dev_ranges", ranges, n)
+    opts = _lib.EmaOpts(float(ema.decay), int(ema.every), int(ema.start_step), int(bool(ema.warmup)), 0)
+    check(lib().goalnet_ema_update_dev_ranges(p.data_ptr(), e.data_ptr(), arr, len(ranges), ctypes.byref(opts), _ctr(step), int(step_bias),
+                                              0 if bad_step is None else _ctr(bad_step), _s()), "ema_update_dev_ranges")
+
+
+def swap_ranges(a, b, ranges):
+    """a[i] <-> b[i] over `ranges` in ONE launch, bit for bit"""
+    _chk(a, b)
+    n = a.numel()
+    _req(a.dtype == F32 and b.dtype == F32 and a.is_contiguous() and b.is_contiguous() and b.numel() == n,
+         "swap_ranges: a and b must be contiguous fp32 arenas of one size")
+    arr = _plain_ranges("swap_ranges", ranges, n)
+    check(lib().goalnet_swap_ranges(a.data_ptr(), b.data_ptr(), arr, len(ranges), _s()), "swap_ranges")
+
+
 def scale_(x, s):
     _chk(x)
     _req(x.dtype == F32 and x.is_contiguous(), "scale_: argument check failed: x.dtype == F32 and x.is_contiguous()")

@@ -15,6 +15,9 @@ EXTENSION: `OptimOptions` — weight decay (coupled as `torch
 `torch.optim.AdamW`), clipping by the global gradient norm (`torch.nn.utils.clip_grad_norm_`) and a learning-rate schedule that the
 device evaluates from its step counter — for `AVM.train_step(optim=)`, `AVM.adam_step(optim=)`, `loop.VideoTrainer(optim=)` and the
 drop-in `Adam(weight_decay=, max_grad_norm=, options=)` / `AdamW`. No AMSGrad, no per-tensor rates.
+
+EXTENSION: `EmaOptions` — an exponential moving average of the weights in a third arena, one launch behind every
+optimizer step, for the same four places (`ema=`); read it with `AVM.ema_of(name)` or evaluate / save under `with model.averaged():`.
 """
 from __future__ import annotations
 
@@ -113,6 +116,58 @@ class OptimOptions:
         return lr
 
 
+@dataclasses.dataclass(frozen=True)
+class EmaOptions:
+    """An exponential moving average of the weights, kept on the device behind every optimizer step. With t the
+    1-based count of applied optimizer steps:
+      start_step   up to here the average is a copy of the weights (it tracks them); averaging begins with step start_step + 1
+      every        afterwards every `every`-th step averages, the others leave the average alone
+      decay        e += (1 - d) (p - e) with d = decay, or
+      warmup       d = min(decay, (1 + k) / (10 + k)) after k averaging updates: a young average forgets its start quickly
+    weight_at() is the closed form; the device evaluates the same from its step counter."""
+    decay: float = 0.999
+    warmup: bool = False
+    every: int = 1
+    start_step: int = 0
+
+    def __post_init__(self):
+        d = self.decay
+        if not isinstance(d, (int, float)) or isinstance(d, bool) or not math.isfinite(d) or not 0.0 <= d < 1.0:
+            raise ValueError(f"decay must be a finite number in [0, 1), got {d!r}")
+        if not isinstance(self.warmup, (bool, int)):
+            raise ValueError(f"warmup must be a bool, got {self.warmup!r}")
+        if not _is_int(self.every) or self.every < 1:
+            raise ValueError(f"every must be an integer >= 1, got {self.every!r}")
+        if not _is_int(self.start_step) or self.start_step < 0:
+            raise ValueError(f"start_step must be an integer >= 0, got {self.start_step!r}")
+        object.__setattr__(self, "decay", float(d))
+        object.__setattr__(self, "warmup", bool(self.warmup))
+
+    def signature(self) -> tuple:
+        """hashable: everything a captured step bakes in about the average"""
+        return (self.decay, self.warmup, self.every, self.start_step)
+
+    def weight_at(self, t: int) -> Optional[float]:
+        """what optimizer step t (1-based) does to the average: 1.0 = a copy of the weights, None = nothing is written, otherwise
+        the fp64 value of 1 - d that the kernel rounds to fp32 — the expression of csrc/ema.hip's ema_plan, operation for operation"""
+        if t <= self.start_step:
+            return 1.0
+        u = t - self.start_step
+        if u % self.every != 0:
+            return None
+        k = u // self.every - 1
+        d = self.decay
+        if self.warmup:
+            d = min(d, float(1 + k) / float(10 + k))
+        return 1.0 - d
+
+
+def _ema(ema):
+    if ema is not None and not isinstance(ema, EmaOptions):
+        raise ValueError("ema must be an optim.EmaOptions")
+    return ema
+
+
 def _options(options, weight_decay, max_grad_norm, decoupled):
     if options is not None:
         if not isinstance(options, OptimOptions):
@@ -129,11 +184,12 @@ class Adam(torch.optim.Optimizer):
     _decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None, weight_decay=None, max_grad_norm=None,
-                 options: Optional[OptimOptions] = None):
+                 options: Optional[OptimOptions] = None, ema: Optional[EmaOptions] = None):
         params = list(params)
         if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameters")
         self.options = _options(options, weight_decay, max_grad_norm, self._decoupled)       # ValueError before anything is launched
+        self.ema = _ema(ema)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._model = model
 
@@ -162,7 +218,7 @@ class Adam(torch.optim.Optimizer):
         if {id(p) for p in g["params"]} not in (every, trainable):
             raise RuntimeError("cvml_goalnet_amd.optim.Adam steps ALL parameters of its AVM (model.parameters()), or all that have "
                                "requires_grad=True (filter(lambda p: p.requires_grad, model.parameters()))")
-        m.adam_step(g["lr"], tuple(g["betas"]), g["eps"], optim=None if self.options.trivial else self.options)
+        m.adam_step(g["lr"], tuple(g["betas"]), g["eps"], optim=None if self.options.trivial else self.options, ema=self.ema)
         return loss
 
     def zero_grad(self, set_to_none: bool = True):
@@ -177,8 +233,8 @@ class AdamW(Adam):
     _decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None, weight_decay=None, max_grad_norm=None,
-                 options: Optional[OptimOptions] = None):
+                 options: Optional[OptimOptions] = None, ema: Optional[EmaOptions] = None):
         if options is None and weight_decay is None:
             weight_decay = 1e-2                     # torch.optim.AdamW's default
         super().__init__(params, lr=lr, betas=betas, eps=eps, model=model, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                         options=options)
+                         options=options, ema=ema)

@@ -138,6 +138,7 @@ PROTOTYPES = {
     "goalnet_conv1d_fwd": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "goalnet_conv1d_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "goalnet_conv1d_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "goalnet_conv1d_bwd_small_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "goalnet_conv1d_bwd_small": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "goalnet_relu_bwd": (c_int, [P, P, P, c_int64, P]),
     "goalnet_mlp_blocks": (c_int, []),

@@ -1289,15 +1289,19 @@ class AVM(_LazyFlags, nn.Module):
                 da2 = torch.empty(n, 128 * l2, dtype=F32, device=dev)
                 ops.linear_bwd_dx(dza, P("audbl.linear3.weight"), da2, mult=None)
                 da1 = torch.empty(n, 64, l1, dtype=F32, device=dev) if conv_a1 else None
-                if n < 64:
-                    # few frames: each Conv1d layer's backward is one launch, its ReLU backward folded into the dz load
+                # few frames: a Conv1d layer's backward is one launch, its ReLU backward folded into the dz load, where the dz rows of a
+                # weight-gradient block fit LDS (n * l1 <= 1536 for conv1, n * l2 <= 3072 for conv2: every n < 64 at 30 bins, n <= 51 at
+                # 60); otherwise, as from 64 frames on, ReLU backward + the multi-launch form, which has no such limit
+                if ops.conv1d_bwd_small_ok(n, 64, l1, 128):
                     ops.conv1d_bwd_small(ctx["a1"], da2, ctx["a2"], P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
-                    if conv_a1:
-                        ops.conv1d_bwd_small(ctx["audio"], da1, ctx["a1"], P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
+                else:
+                    ops.relu_bwd(da2, a2f, da2)
+                    ops.conv1d_bwd(ctx["a1"], da2, P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
+                if not conv_a1:
                     return
-                ops.relu_bwd(da2, a2f, da2)
-                ops.conv1d_bwd(ctx["a1"], da2, P("audbl.conv2.weight"), da1, G("audbl.conv2.weight"), G("audbl.conv2.bias"), n, 64, l1, 128)
-                if conv_a1:
+                if ops.conv1d_bwd_small_ok(n, 30, bins, 64):
+                    ops.conv1d_bwd_small(ctx["audio"], da1, ctx["a1"], P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
+                else:
                     ops.relu_bwd(da1, ctx["a1"], da1)
                     ops.conv1d_bwd(ctx["audio"], da1, P("audbl.conv1.weight"), d_audio, G("audbl.conv1.weight"), G("audbl.conv1.bias"), n, 30, bins, 64)
             fork.run(audbl_bwd, dz, d_audio)
@@ -1512,6 +1516,12 @@ class AVM(_LazyFlags, nn.Module):
                 raise RuntimeError(f"weights must be a float32 tensor of {n0} elements")
         if loss_kind != "mse_bcast" and self.stat_sync is not None:
             raise GoalnetError("global-batch mode is defined for the broadcast MSE only: loss='mse_bcast'")
+        if not torch.is_tensor(labels) or labels.numel() != n0:
+            raise RuntimeError(f"labels must be a tensor of {n0} elements, one per frame")
+        # the inputs as forward() takes them, the labels as one flat row: any device, any float or integer type, any strides. The kernels
+        # read bare pointers and element counts. Contiguous fp32 tensors on the device pass through as they are (no copy, no launch).
+        audio, visual, _ = self._to_device_inputs(audio, visual)
+        labels = labels.detach().to(device=self._device, dtype=F32).reshape(-1).contiguous()
         if weights is not None:
             weights = weights.detach().to(self._device).reshape(-1).contiguous()
         frozen = self._frozen_names()                   # requires_grad=False: no gradient, no update, no step counted
@@ -1520,8 +1530,7 @@ class AVM(_LazyFlags, nn.Module):
         loss = torch.empty(1, dtype=F32, device=self._device)
         dout = torch.empty(n0 if self.head == "regression" else (n0, self.num_classes), dtype=F32, device=self._device)
         # the regression head's broadcast MSE is evaluated by the fused MLP launch itself where that launch exists (<= 16 rows)
-        lab32 = labels if (torch.is_tensor(labels) and labels.dtype == F32 and labels.is_contiguous() and labels.is_cuda) else None
-        fused_loss = (lab32, loss, dout) if (self.stat_sync is None and lab32 is not None and self._mlp_fused(n0)) else None
+        fused_loss = (labels, loss, dout) if (self.stat_sync is None and self._mlp_fused(n0)) else None
         # the dropout draw counter advances with the step's other counters, in the one launch at the end
         out, ctx = self.forward_device(audio, visual, save=True, fused_loss=fused_loss, caller_ticks=True,
                                        fused_loss_kind=None if loss_kind == "mse_bcast" else (loss_kind, loss_param, weights))
@@ -1531,16 +1540,16 @@ class AVM(_LazyFlags, nn.Module):
         if ctx["loss_done"]:
             pass
         elif loss_kind != "mse_bcast":
-            ops.frame_loss(out, labels.to(device=self._device, dtype=F32).reshape(-1).contiguous(), loss, dout, loss_kind, loss_param, weights)
+            ops.frame_loss(out, labels, loss, dout, loss_kind, loss_param, weights)
         elif self.head == "classifier":
             if self.stat_sync is not None:
                 raise GoalnetError("global-batch mode is defined for the regression head's broadcast MSE only")
-            ops.cross_entropy(out, labels.to(F32), loss, dout)          # main.py:69, 189: CrossEntropyLoss(pred, (labels-1).long())
+            ops.cross_entropy(out, labels, loss, dout)          # main.py:69, 189: CrossEntropyLoss(pred, (labels-1).long())
         elif self.stat_sync is not None:
             # the (N, N) broadcast couples every prediction with every label of the batch: evaluate it on the rank-ordered
             # concatenation and keep this rank's slice of dL/dp
             gout = torch.empty(n * self.stat_sync.world, dtype=F32, device=self._device)
-            ops.mse_bcast(self.stat_sync.gather(out), self.stat_sync.gather(labels.to(F32)), loss, gout)
+            ops.mse_bcast(self.stat_sync.gather(out), self.stat_sync.gather(labels), loss, gout)
             dout = gout[n * self.stat_sync.rank: n * (self.stat_sync.rank + 1)]
         else:
             ops.mse_bcast(out, labels, loss, dout)

@@ -570,6 +570,14 @@ int goalnet_conv1d_bwd(const float* x, const float* dz, const float* w, float* d
     return 0;
 }
 
+/* whether goalnet_conv1d_bwd_small serves the dims: its own dim checks, and the dz rows a weight-gradient block keeps in LDS */
+int goalnet_conv1d_bwd_small_ok(int N, int Cin, int L, int Cout, int stride, int pad) {
+    if (!(N > 0 && N < 64 && Cin > 0 && Cin <= 256 && L > 0 && Cout > 0 && stride > 0 && pad >= 0 && L + 2 * pad >= 3)) return 0;
+    const int64_t Lo = (L + 2 * pad - 3) / stride + 1;
+    const int64_t cpb = 256 / Cin;
+    return (int64_t)N * cpb * Lo * (int64_t)sizeof(float) <= 48 * 1024;          // the dz rows a weight-gradient block keeps in LDS
+}
+
 /* goalnet_conv1d_bwd for few frames (N < 64) in ONE launch, with the ReLU backward of the layer's own output folded in:
  * y (nullable) = the layer's ReLU output, effective dz = dz * (y > 0). dx nullable (first layer). Cin <= 256. */
 int goalnet_conv1d_bwd_small(const float* x, const float* dz, const float* y, const float* w, float* dx, float* dw, float* db,
@@ -577,10 +585,11 @@ int goalnet_conv1d_bwd_small(const float* x, const float* dz, const float* y, co
     GN_REQUIRE(x && dz && w && dw && db, GOALNET_E_NULL, "conv1d_bwd_small: null pointer");
     GN_REQUIRE(N > 0 && N < 64 && Cin > 0 && Cin <= 256 && L > 0 && Cout > 0 && stride > 0 && pad >= 0 && L + 2 * pad >= 3, GOALNET_E_SHAPE,
                "conv1d_bwd_small: bad dims (N < 64, Cin <= 256)");
+    GN_REQUIRE(goalnet_conv1d_bwd_small_ok(N, Cin, L, Cout, stride, pad), GOALNET_E_SHAPE,
+               "conv1d_bwd_small: the dz rows of a block do not fit LDS (ask goalnet_conv1d_bwd_small_ok; use goalnet_relu_bwd + goalnet_conv1d_bwd)");
     const int Lo = (L + 2 * pad - 3) / stride + 1;
     const int cpb = 256 / Cin;
     const size_t lds = (size_t)N * cpb * Lo * sizeof(float);
-    GN_REQUIRE(lds <= 48 * 1024, GOALNET_E_SHAPE, "conv1d_bwd_small: the dz rows of a block do not fit LDS");
     const int nA = (Cout + cpb - 1) / cpb;
     const int nB = dx ? (int)grid1d((int64_t)N * Cin * L * 16) : 0;
     hipLaunchKernelGGL(conv1d_bwd_small_kernel, dim3(nA + nB), dim3(256), lds, (hipStream_t)stream, x, dz, y, w, dx, dw, db,

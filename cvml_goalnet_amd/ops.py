@@ -25,14 +25,22 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
-def _chk(*ts):
+def _chk(*ts, f64=True):
+    """f64=False: the wrapper takes no float64 tensor (no fp64 partial sums, no workspace of the caller's): one that arrives is an fp32
+    tensor that was never converted, and its bytes would be read as twice as many floats"""
     for t in ts:
         if t is None:
             continue
         if not t.is_cuda:
             raise _lib.GoalnetError("expected a GPU tensor")
-        if t.dtype not in (F32, torch.float64, torch.uint8, torch.bfloat16, torch.float16, torch.int32):
+        if t.dtype not in (F32, torch.float64, torch.uint8, torch.bfloat16, torch.float16, torch.int32) or (t.dtype == torch.float64 and not f64):
             raise _lib.GoalnetError(f"unexpected dtype {t.dtype}")
+
+
+def _f32c(who, **ts):
+    """every tensor given is fp32 and contiguous: the kernels behind `who` take a bare pointer and an element count"""
+    for name, t in ts.items():
+        _req(t is None or (t.dtype == F32 and t.is_contiguous()), f"{who}: {name} must be a contiguous float32 tensor")
 
 
 def _req(cond, msg):
@@ -90,7 +98,8 @@ def conv3x3_weight_flip2(wa, wta, couta, cina, wb, wtb, coutb, cinb):
 
 
 def conv1_fwd(x_nchw, w, b, y, N, H, W):
-    _chk(x_nchw, w, b, y)
+    _chk(x_nchw, w, b, y, f64=False)
+    _f32c("conv1_fwd", x_nchw=x_nchw, w=w, b=b, y=y)
     _req(x_nchw.is_contiguous() and x_nchw.numel() == N * 3 * H * W, "conv1_fwd: argument check failed: x_nchw.is_contiguous() and x_nchw.numel() == N * 3 * H * W")
     Ho, Wo = (H + 3) // 3 + 1, (W + 3) // 3 + 1
     _req(y.numel() == N * Ho * Wo * 64 and w.numel() == 64 * 27 and b.numel() == 64, "conv1_fwd: argument check failed: y.numel() == N * Ho * Wo * 64 and w.numel() == 64 * 27 and b.numel() == 64")
@@ -99,8 +108,10 @@ def conv1_fwd(x_nchw, w, b, y, N, H, W):
 
 
 def conv1_wgrad(x_nchw, dy, dw, db, N, H, W):
-    _chk(x_nchw, dy, dw, db)
+    _chk(x_nchw, dy, dw, db, f64=False)
+    _f32c("conv1_wgrad", x_nchw=x_nchw, dy=dy, dw=dw, db=db)
     Ho, Wo = (H + 3) // 3 + 1, (W + 3) // 3 + 1
+    _req(x_nchw.numel() == N * 3 * H * W, "conv1_wgrad: argument check failed: x_nchw.numel() == N * 3 * H * W")
     _req(dy.numel() == N * Ho * Wo * 64 and dw.numel() == 64 * 27 and db.numel() == 64, "conv1_wgrad: argument check failed: dy.numel() == N * Ho * Wo * 64 and dw.numel() == 64 * 27 and db.numel() == 64")
     nbytes = lib().goalnet_conv1_wgrad_ws_bytes(N, H, W)
     ws = torch.empty(nbytes // 4, dtype=F32, device=dy.device)
@@ -687,7 +698,8 @@ def mul(x, m, y):
 
 
 def conv1d_fwd(x, w, b, y, relu, N, Cin, L, Cout, stride=2, pad=1):
-    _chk(x, w, b, y)
+    _chk(x, w, b, y, f64=False)
+    _f32c("conv1d_fwd", x=x, w=w, b=b, y=y)
     Lo = (L + 2 * pad - 3) // stride + 1
     _req(x.numel() == N * Cin * L and y.numel() == N * Cout * Lo and w.numel() == Cout * Cin * 3, "conv1d_fwd: argument check failed: x.numel() == N * Cin * L and y.numel() == N * Cout * Lo and w.numel() == Cout * Cin * 3")
     check(lib().goalnet_conv1d_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), int(relu), y.data_ptr(), N, Cin, L, Cout, stride, pad,
@@ -696,18 +708,27 @@ def conv1d_fwd(x, w, b, y, relu, N, Cin, L, Cout, stride=2, pad=1):
 
 
 def conv1d_bwd(x, dz, w, dx, dw, db, N, Cin, L, Cout, stride=2, pad=1):
-    _chk(x, dz, w, dx, dw, db)
+    _chk(x, dz, w, dx, dw, db, f64=False)
+    _f32c("conv1d_bwd", x=x, dz=dz, w=w, dx=dx, dw=dw, db=db)
     Lo = (L + 2 * pad - 3) // stride + 1
     _req(x.numel() == N * Cin * L and dz.numel() == N * Cout * Lo, "conv1d_bwd: argument check failed: x.numel() == N * Cin * L and dz.numel() == N * Cout * Lo")
+    _req(w.numel() == dw.numel() == Cout * Cin * 3 and db.numel() == Cout and (dx is None or dx.numel() == x.numel()), "conv1d_bwd: w / dw / db / dx shapes")
     nbytes = lib().goalnet_conv1d_bwd_ws_bytes(N, Cin, Cout)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device) if nbytes else None
     check(lib().goalnet_conv1d_bwd(x.data_ptr(), dz.data_ptr(), w.data_ptr(), _p(dx), dw.data_ptr(), db.data_ptr(), N, Cin, L, Cout,
                                    stride, pad, _p(ws), nbytes, _s()), "conv1d_bwd")
 
 
+def conv1d_bwd_small_ok(N, Cin, L, Cout, stride=2, pad=1) -> bool:
+    """whether conv1d_bwd_small serves the dims (N < 64, Cin <= 256, and the dz rows of a weight-gradient block fit LDS); where it
+    does not, relu_bwd + conv1d_bwd compute the same layer backward in several launches"""
+    return bool(lib().goalnet_conv1d_bwd_small_ok(N, Cin, L, Cout, stride, pad))
+
+
 def conv1d_bwd_small(x, dz, y, w, dx, dw, db, N, Cin, L, Cout, stride=2, pad=1):
-    """conv1d_bwd for N < 64 frames in one launch; y (the layer's ReLU output) gates dz when given"""
-    _chk(x, dz, y, w, dx, dw, db)
+    """conv1d_bwd for N < 64 frames in one launch; y (the layer's ReLU output) gates dz when given; only for dims conv1d_bwd_small_ok accepts"""
+    _chk(x, dz, y, w, dx, dw, db, f64=False)
+    _f32c("conv1d_bwd_small", x=x, dz=dz, y=y, w=w, dx=dx, dw=dw, db=db)
     Lo = (L + 2 * pad - 3) // stride + 1
     _req(x.numel() == N * Cin * L and dz.numel() == N * Cout * Lo and (y is None or y.numel() == dz.numel()), "conv1d_bwd_small: x / dz / y shapes")
     _req(dw.numel() == Cout * Cin * 3 and db.numel() == Cout and (dx is None or dx.numel() == x.numel()), "conv1d_bwd_small: dw / db / dx shapes")
@@ -855,7 +876,8 @@ def cls_head_fwd(h, w, b, logits, scores):
 
 def cross_entropy(scores, labels, loss, dscores):
     """nn.CrossEntropyLoss()(scores, (labels - 1).long()) and its gradient wrt scores"""
-    _chk(scores, labels, loss, dscores)
+    _chk(scores, labels, loss, dscores, f64=False)
+    _f32c("cross_entropy", scores=scores, labels=labels, loss=loss, dscores=dscores)
     N, C = scores.shape
     _req(labels.numel() == N and scores.is_contiguous() and (dscores is None or dscores.is_contiguous()), "cross_entropy: argument check failed: labels.numel() == N and scores.is_contiguous() and (dscores is None or dscores.is_contiguous())")
     check(lib().goalnet_cross_entropy(scores.data_ptr(), labels.data_ptr(), _p(loss), _p(dscores), N, C, _s()), "cross_entropy")
@@ -880,7 +902,8 @@ def argmax_plus1(scores, classes):
 
 
 def mse_bcast(pred, labels, loss, dpred):
-    _chk(pred, labels, loss, dpred)
+    _chk(pred, labels, loss, dpred, f64=False)
+    _f32c("mse_bcast", pred=pred, labels=labels, loss=loss, dpred=dpred)
     N = pred.numel()
     _req(labels.numel() == N, "mse_bcast: argument check failed: labels.numel() == N")
     check(lib().goalnet_mse_bcast(pred.data_ptr(), labels.data_ptr(), N, _p(loss), _p(dpred), _s()), "mse_bcast")

@@ -318,7 +318,11 @@ size_t goalnet_conv1d_bwd_ws_bytes(int N, int Cin, int Cout);
 int goalnet_conv1d_bwd(const float* x, const float* dz, const float* w, float* dx, float* dw, float* db,
                        int N, int Cin, int L, int Cout, int stride, int pad, void* ws, size_t ws_bytes, void* stream);
 /* the same for few frames (N < 64: the reference's sub-batches) in ONE launch, with the layer's own ReLU backward folded in:
- * y (nullable) = the layer's ReLU output, the effective output gradient is dz * (y > 0); dx nullable; Cin <= 256 */
+ * y (nullable) = the layer's ReLU output, the effective output gradient is dz * (y > 0); dx nullable; Cin <= 256.
+ * A weight-gradient block keeps the dz rows of its 256 / Cin output channels for all N frames in LDS (N * (256 / Cin) * Lo floats,
+ * 48 KB at the most): goalnet_conv1d_bwd_small_ok() says whether the dims are served; otherwise use goalnet_relu_bwd +
+ * goalnet_conv1d_bwd, which have no such limit. */
+int goalnet_conv1d_bwd_small_ok(int N, int Cin, int L, int Cout, int stride, int pad);
 int goalnet_conv1d_bwd_small(const float* x, const float* dz, const float* y, const float* w, float* dx, float* dw, float* db,
                              int N, int Cin, int L, int Cout, int stride, int pad, void* stream);
 /* dz = dy * (y > 0) */

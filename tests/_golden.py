@@ -25,6 +25,7 @@ class Golden:
         self.n = int(self.z["meta|n"][0]); self.h = int(self.z["meta|h"][0])
         self.steps = int(self.z["meta|steps"][0]); self.audio = bool(self.z["meta|audio"][0])
         self.drop = bool(self.z["meta|drop"][0])
+        self.bins = int(self.z["meta|bins"][0]) if "meta|bins" in self.z.files else 30      # audio bin length; stored where it is not 30
 
     def keys(self, prefix):
         return sorted({k.split("|")[0] for k in self.z.files if k.startswith(prefix)})
@@ -73,7 +74,7 @@ class Golden:
 
 
 GOLDEN_CASES_SMALL = ["avm_a1_n10_h40_p0", "avm_a1_n10_h40_mask3", "avm_a0_n10_h40_mask", "avm_a1_n1_h40_p0",
-                      "avm_a1_n16_h40_mask", "avm_a0_n7_h52_p0"]
+                      "avm_a1_n16_h40_mask", "avm_a0_n7_h52_p0", "avm_a1_n10_h40_b60_p0", "avm_a1_n7_h40_b17_mask"]
 GOLDEN_CASES_BIG = ["avm_a1_n2_h224_p0"]
 
 

@@ -2,6 +2,8 @@
 `head`, `audio_included` and train / eval mode, at 40 x 40 frames, bins = 30 and n in {10, 32} (n = 10: the skinny linear5, the fused MLP
 of the regression head, the one-launch BatchNorm kernels; n = 32: the 16-bit linear5 / p3 / y3 and the unfused MLP). SHAPE_CELLS runs five
 of the cells again on four frames with H != W, where the host code's (h, w) bookkeeping can be wrong without a square frame noticing.
+BIN_CELLS are six audio cells at bin lengths other than 30 (tests/_bin_classes.py says which kernel class each is here for); they run
+in tests/test_gpu_bin_classes.py.
 
 Three parts, so that the comparison can be run — and broken on purpose — without a GPU (tests/test_mode_matrix_host.py):
 
@@ -29,6 +31,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+import _bin_classes as BC
 import eval_ref
 from _decisions import MLP_LAYERS, NEAR_TIE, decisions, judge, report_lines, storage_noise, totals
 from cvml_goalnet_amd import synth
@@ -45,7 +48,8 @@ GUARD_GRADS = ("visbl.conv3.weight", "visbl.linear5.weight")
 # tells a row of the classifier's loss from another: swapping the two frames would be a symmetry of the step, invisible in every gradient
 LABEL_SEED = synth.BASE_SEED + 1
 
-Cell = namedtuple("Cell", "precision head audio mode n hw", defaults=(HW,))
+BINS = 30                 # the audio bin length of the committed mode matrix; BIN_CELLS below carries its own
+Cell = namedtuple("Cell", "precision head audio mode n hw bins", defaults=(HW, BINS))
 
 # precision x head x audio x mode x n: every combination of levels of any three factors appears (asserted by
 # tests/test_mode_matrix_host.py). Written out by hand; nothing is generated at run time.
@@ -121,9 +125,18 @@ SHAPE_CELLS = tuple(c for c, _ in _SHAPE_ROWS)
 SHAPE_LAUNCHES = dict(_SHAPE_ROWS)
 
 
+# ---- audio bin lengths other than 30 (tests/_bin_classes.py: the rows and the class each is here for) ---------------------------------
+# (head, mode, n, bins) -> seed of the audio input where the default one does not do. The fp32 classifier cell at 17 bins: with the default
+# seed the ORACLE alone leaves a row with a top-2 score gap of 2.7e-5 <= CLASS_GAP, and compare() excludes no row; seeds + 1 .. + 5 give
+# 1.6e-4, 1.5e-4, 5.7e-4, 4.4e-4, 6.0e-4 (measured on the oracle, no device involved)
+AUDIO_SEED = {("classifier", "eval", 32, 17): synth.BASE_SEED + 3}
+BIN_CELLS = tuple(Cell(precision, head, True, mode, n, HW, bins) for (precision, head, mode, n, bins), _ in BC.STEP_CELLS)
+
+
 def cell_id(c):
     shape = "" if c.hw == HW else f"-{c.hw[0]}x{c.hw[1]}"
-    return f"{c.precision}-{c.head}-{'audio' if c.audio else 'noaudio'}-{c.mode}-n{c.n}{shape}"
+    bins = "" if c.bins == BINS else f"-b{c.bins}"
+    return f"{c.precision}-{c.head}-{'audio' if c.audio else 'noaudio'}-{c.mode}-n{c.n}{shape}{bins}"
 
 
 def is_fp32(c):
@@ -157,19 +170,19 @@ def converged_stats(p, aud, vis, audio, head, seed=2025):
     return b
 
 
-def fixture(head, audio, mode, n, hw=HW):
-    """everything a cell starts from, at frames of hw = (H, W), as CPU tensors that nobody modifies (callers clone what a step updates
-    in place)"""
-    return _fixture(head, audio, mode, n, tuple(hw))
+def fixture(head, audio, mode, n, hw=HW, bins=BINS):
+    """everything a cell starts from, at frames of hw = (H, W) and `bins` audio bins, as CPU tensors that nobody modifies (callers clone
+    what a step updates in place)"""
+    return _fixture(head, audio, mode, n, tuple(hw), bins)
 
 
 @functools.lru_cache(maxsize=None)
-def _fixture(head, audio, mode, n, hw):
+def _fixture(head, audio, mode, n, hw, bins):
     h, w = hw
-    params = eval_ref.classifier_params(h, audio, w=w) if head == "classifier" else synth.make_params(h, w, 30, audio)
+    params = eval_ref.classifier_params(h, audio, w=w, bins=bins) if head == "classifier" else synth.make_params(h, w, bins, audio)
     fx = {"p": {k: torch.from_numpy(v.copy()) for k, v in params.items()},
           "vis": torch.from_numpy(synth.make_visual(n, h, w)),
-          "aud": torch.from_numpy(synth.make_audio(n)) if audio else None,
+          "aud": torch.from_numpy(synth.make_audio(n, bins, seed=AUDIO_SEED.get((head, mode, n, bins), synth.BASE_SEED))) if audio else None,
           "lab": torch.from_numpy(synth.make_labels(n, seed=LABEL_SEED))}
     if mode == "train":
         fx["masks"] = [torch.from_numpy(m) for m in synth.make_drop_masks(n, step=0)]
@@ -181,7 +194,7 @@ def _fixture(head, audio, mode, n, hw):
 
 
 def fixture_of(c):
-    return fixture(c.head, c.audio, c.mode, c.n, c.hw)
+    return fixture(c.head, c.audio, c.mode, c.n, c.hw, c.bins)
 
 
 def loss_fn(c):
@@ -354,7 +367,8 @@ def compare(c, fx, dev, log=print):
 def run_device(c, fx, monkeypatch):
     """one train_step of the cell on the GPU. Returns the dict compare() reads; asserts what only the device can answer: the kernels the
     mode selects ran (non-vacuity), eval mode moved no counter, fp16 overflowed nowhere. Two entries are for the caller's own non-vacuity
-    assertions and are not read by compare(): "launches" = calls of (pool_bn_fwd_small, pool_bnstats_fwd, pool_bn_eval_fwd), "saved" =
+    assertions and are not read by compare(): "launches" = calls of (pool_bn_fwd_small, pool_bnstats_fwd, pool_bn_eval_fwd),
+    "conv1d_launches" = calls of (conv1d_bwd_small, conv1d_bwd), "saved" =
     (shape, dtype) of the pooled activations and 16-bit operands the context holds."""
     from cvml_goalnet_amd import AVM
     from test_gpu_eval import Counter
@@ -371,6 +385,7 @@ def run_device(c, fx, monkeypatch):
     m.keep_ctx = True
     pool_eval, pool_stats = Counter(monkeypatch, "pool_bn_eval_fwd"), Counter(monkeypatch, "pool_bnstats_fwd")
     pool_small = Counter(monkeypatch, "pool_bn_fwd_small")
+    c1d_small, c1d_multi = Counter(monkeypatch, "conv1d_bwd_small"), Counter(monkeypatch, "conv1d_bwd")
     drop0 = m._drop_step
     ctr0 = None if m._state is None else m._state.tolist()
     loss, pred = m.train_step(None if fx["aud"] is None else fx["aud"].to(DEV), fx["vis"].to(DEV), fx["lab"].to(DEV), lr=LR)
@@ -401,7 +416,7 @@ def run_device(c, fx, monkeypatch):
            "grads": {k: m.grad_of(k).cpu() for k in fx["p"]}, "params": {k: sd1[k].cpu() for k in fx["p"]},
            "bufs": {k: sd1[k].cpu() for k in fx["b"]},
            "classes": m.predict_classes(pred).cpu() if c.head == "classifier" else None,
-           "launches": (pool_small.calls, pool_stats.calls, pool_eval.calls),
+           "launches": (pool_small.calls, pool_stats.calls, pool_eval.calls), "conv1d_launches": (c1d_small.calls, c1d_multi.calls),
            "saved": {k: (tuple(ctx[k].shape), ctx[k].dtype) for k in ("p1", "p2", "p3", "xh1", "xh2", "xh3") if ctx.get(k) is not None}}
     del ctx
     return dev

@@ -14,7 +14,7 @@ does, and
      regenerated from cvml_goalnet_amd/synth.py's seed formula on both sides.
 
 Nothing here runs on the GPU box; /root/reference does not exist there.
-Usage:  python tests/golden/make_golden.py [--only NAME_SUBSTR]
+Usage:  python tests/golden/make_golden.py [--only NAME_SUBSTR] [--out DIR]
 """
 from __future__ import annotations
 
@@ -162,11 +162,11 @@ def _reference_steps(utils, n, h, audio_included, drop, steps, params_np, aud, v
     return fx, kept
 
 
-def run_case(utils, name, n, h, audio_included, drop, steps, out_dir):
-    print(f"== {name}: N={n} H=W={h} audio={audio_included} dropout={drop} steps={steps}", flush=True)
+def run_case(utils, name, n, h, audio_included, drop, steps, bins, out_dir):
+    print(f"== {name}: N={n} H=W={h} audio={audio_included} bins={bins} dropout={drop} steps={steps}", flush=True)
     big = h > 100   # 1.29 G parameters: run reference and restatement one after the other, compare summaries
-    params_np = synth.make_params(h, h, 30, audio_included)
-    aud, vis, lab = build_inputs(n, h, audio_included)
+    params_np = synth.make_params(h, h, bins, audio_included)
+    aud, vis, lab = build_inputs(n, h, audio_included, bins)
 
     fx, kept = _reference_steps(utils, n, h, audio_included, drop, steps, params_np, aud, vis, lab, not big)
 
@@ -231,6 +231,8 @@ def run_case(utils, name, n, h, audio_included, drop, steps, out_dir):
         raise SystemExit(f"restatement disagrees with the reference: {bad}")
     fx["meta|n"] = np.array([n]); fx["meta|h"] = np.array([h]); fx["meta|steps"] = np.array([steps])
     fx["meta|audio"] = np.array([int(audio_included)]); fx["meta|drop"] = np.array([0 if drop == "p0" else 1])
+    if bins != 30:
+        fx["meta|bins"] = np.array([bins])              # absent = 30: the fixtures written before the column existed stay byte for byte
     fx["meta|bit_equal"] = np.array([n_eq, len(equal_report)])
     fx["meta|worst_rel"] = np.array([worst[1][2]])
     fx["meta|torch"] = np.array([ord(c) for c in torch.__version__], dtype=np.int64)
@@ -238,27 +240,31 @@ def run_case(utils, name, n, h, audio_included, drop, steps, out_dir):
 
 
 CASES = [
-    # name, N, H, audio, dropout, steps
-    ("avm_a1_n10_h40_p0", 10, 40, True, "p0", 1),
-    ("avm_a1_n10_h40_mask3", 10, 40, True, "mask", 3),
-    ("avm_a0_n10_h40_mask", 10, 40, False, "mask", 1),
-    ("avm_a1_n1_h40_p0", 1, 40, True, "p0", 1),
-    ("avm_a1_n16_h40_mask", 16, 40, True, "mask", 1),
-    ("avm_a0_n7_h52_p0", 7, 52, False, "p0", 1),
-    ("avm_a1_n2_h224_p0", 2, 224, True, "p0", 1),
+    # name, N, H, audio, dropout, steps, audio bins
+    ("avm_a1_n10_h40_p0", 10, 40, True, "p0", 1, 30),
+    ("avm_a1_n10_h40_mask3", 10, 40, True, "mask", 3, 30),
+    ("avm_a0_n10_h40_mask", 10, 40, False, "mask", 1, 30),
+    ("avm_a1_n1_h40_p0", 1, 40, True, "p0", 1, 30),
+    ("avm_a1_n16_h40_mask", 16, 40, True, "mask", 1, 30),
+    ("avm_a0_n7_h52_p0", 7, 52, False, "p0", 1, 30),
+    ("avm_a1_n2_h224_p0", 2, 224, True, "p0", 1, 30),
+    # other bin lengths: K of audbl.linear3 = 128 * l2 = 1920 (60 bins), 640 (17 bins: odd B, odd l1)
+    ("avm_a1_n10_h40_b60_p0", 10, 40, True, "p0", 1, 60),
+    ("avm_a1_n7_h40_b17_mask", 7, 40, True, "mask", 1, 17),
 ]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
+    ap.add_argument("--out", default=HERE, help="directory the fixtures are written to")
     args = ap.parse_args()
     torch.set_num_threads(8)
     utils = import_reference()
     for c in CASES:
         if args.only and args.only not in c[0]:
             continue
-        run_case(utils, *c, out_dir=HERE)
+        run_case(utils, *c, out_dir=args.out)
 
 
 if __name__ == "__main__":

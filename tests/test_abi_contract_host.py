@@ -222,7 +222,7 @@ ROWS["goalnet_conv1d_bwd"] = row([A, A2, A3, None, A4, A, 515, 30, 30, 64, 2, 1,
 # no error path: sizes, names, predicates and constants; each is checked against its header comment further down
 NO_ERROR_PATH = {n for n, (res, _) in _lib.PROTOTYPES.items() if res is not ctypes.c_int} | {
     "goalnet_abi_version", "goalnet_stat_parts", "goalnet_mlp_blocks", "goalnet_linear_split_ok", "goalnet_linear_bwd_dx_bf16_o16_ok",
-    "goalnet_conv3x3_fwd_bf16p_o16_ok"}
+    "goalnet_conv3x3_fwd_bf16p_o16_ok", "goalnet_conv1d_bwd_small_ok"}
 # argument lists that the table cannot express: segment structs (test_row_copy_segments_are_checked) and host out-pointers
 # (test_bf16_padded_layout_refuses_bad_arguments)
 STRUCT_ROWS = {"goalnet_rows_copy_batch", "goalnet_rows_scatter_tick", "goalnet_bf16_padded_layout"}
@@ -398,3 +398,13 @@ def test_served_predicates_agree_with_their_entry_points(monkeypatch):
             _refused(lib, "goalnet_linear_fwd_split", args, E_SHAPE, f"parts {parts}, dims {dims}")
     for parts in (0, 1, 4):
         assert lib.goalnet_linear_split_ok(parts, *LSPLIT) == 0
+    # goalnet_conv1d_bwd_small_ok: N < 64, Cin <= 256 and N * (256 / Cin) * Lo floats of dz within 48 KB (the header's comment); the row's
+    # own dims are served, and tests/test_bin_classes_host.py walks every (N, B) of the two AudBl layers against the rule
+    small_row = ROWS["goalnet_conv1d_bwd_small"]["args"]
+    assert lib.goalnet_conv1d_bwd_small_ok(*small_row[7:13]) == 1
+    for dims in [(52, 30, 60, 64, 2, 1), (62, 64, 100, 128, 2, 1), (64, 30, 30, 64, 2, 1), (4, 257, 30, 64, 2, 1), (0, 30, 30, 64, 2, 1)]:
+        assert lib.goalnet_conv1d_bwd_small_ok(*dims) == 0, dims
+        args = list(small_row)
+        args[7:13] = dims
+        _refused(lib, "goalnet_conv1d_bwd_small", args, E_SHAPE, f"dims {dims}")
+    assert lib.goalnet_conv1d_bwd_small_ok(51, 30, 60, 64, 2, 1) == 1 and lib.goalnet_conv1d_bwd_small_ok(61, 64, 100, 128, 2, 1) == 1

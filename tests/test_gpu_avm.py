@@ -30,9 +30,9 @@ def load_model(h, audio, bins=30, dropout="device"):
     return m, params
 
 
-def inputs(n, h, audio):
+def inputs(n, h, audio, bins=30):
     vis = torch.from_numpy(synth.make_visual(n, h, h))
-    aud = torch.from_numpy(synth.make_audio(n)) if audio else [None] * n
+    aud = torch.from_numpy(synth.make_audio(n, bins)) if audio else [None] * n
     lab = torch.from_numpy(synth.make_labels(n))
     return aud, vis, lab
 
@@ -85,9 +85,9 @@ def routing_disagreements(inter, taps):
 @pytest.mark.parametrize("case", GOLDEN_CASES_SMALL + GOLDEN_CASES_BIG)
 def test_fused_train_steps_match_reference_goldens(case):
     g = Golden(case)
-    model, params = load_model(g.h, g.audio, dropout="device" if g.drop else "off")
+    model, params = load_model(g.h, g.audio, bins=g.bins, dropout="device" if g.drop else "off")
     model.keep_ctx = True
-    aud, vis, lab = inputs(g.n, g.h, g.audio)
+    aud, vis, lab = inputs(g.n, g.h, g.audio, g.bins)
     audg = aud.to(DEV) if g.audio else None
     visg, labg = vis.to(DEV), lab.to(DEV)
     big = g.h > 100

@@ -22,9 +22,9 @@ DEV = "cuda:0"
 LR = 1e-3
 
 
-def load_model(h, audio, precision="fp32", head="regression", w=None):
+def load_model(h, audio, precision="fp32", head="regression", w=None, bins=30):
     w = h if w is None else w
-    params = eval_ref.classifier_params(h, audio, w=w) if head == "classifier" else synth.make_params(h, w, 30, audio)
+    params = eval_ref.classifier_params(h, audio, w=w, bins=bins) if head == "classifier" else synth.make_params(h, w, bins, audio)
     m = AVM(audio_included=audio, device=DEV, precision=precision, seed=synth.BASE_SEED, head=head)
     sd = {k: torch.from_numpy(v) for k, v in params.items()}
     sd.update(avm_ref.init_buffers())
@@ -93,9 +93,9 @@ def test_device_counter_kernels_match_their_host_scalar_twins():
     assert torch.equal(pc, pd)
 
 
-def _video(n, h, audio, salt, w=None):
+def _video(n, h, audio, salt, w=None, bins=30):
     vis = torch.from_numpy(synth.make_visual(n, h, h if w is None else w, seed=synth.BASE_SEED + salt))
-    aud = torch.from_numpy(synth.make_audio(n, seed=synth.BASE_SEED + salt)) if audio else [None] * n
+    aud = torch.from_numpy(synth.make_audio(n, bins, seed=synth.BASE_SEED + salt)) if audio else [None] * n
     lab = torch.from_numpy(synth.make_labels(n, seed=synth.BASE_SEED + salt))
     return aud, vis, lab
 
@@ -133,13 +133,15 @@ def test_graph_loop_equals_eager_train_steps_bit_for_bit_on_non_square_frames():
     assert tr._key == ((64, 40), 30) and tr._vid.shape[1:] == (3, 64, 40)
 
 
-def _graph_loop_vs_eager(audio, precision, head, sb, hw, frames, counts, captured):
+def _graph_loop_vs_eager(audio, precision, head, sb, hw, frames, counts, captured, bins=None):
     """VideoTrainer against the eager sequence of train_step calls on videos of `frames` frames of hw = (H, W): losses, predictions,
     the state dict, the counters and the Adam moments bit for bit; `counts` = the (eager steps, replays) the caller worked out by
-    hand, `captured` = the sub-batch sizes that end up with a graph"""
+    hand, `captured` = the sub-batch sizes that end up with a graph; `bins` = the audio bin length of each video (None: 30), all with
+    the l2 of the first, which sizes audbl.linear3"""
     h, w = hw
-    videos = [_video(f, h, audio, 1 + i, w=w) for i, f in enumerate(frames)]
-    eager, graphed = load_model(h, audio, precision, head, w=w), load_model(h, audio, precision, head, w=w)
+    bins = (30,) * len(frames) if bins is None else bins
+    videos = [_video(f, h, audio, 1 + i, w=w, bins=b) for i, (f, b) in enumerate(zip(frames, bins))]
+    eager, graphed = load_model(h, audio, precision, head, w=w, bins=bins[0]), load_model(h, audio, precision, head, w=w, bins=bins[0])
     tr = VideoTrainer(graphed, subbatch_size=sb, lr=LR)
     for aud, vis, lab in videos:
         # eager: the reference's loop, main.py:177-196, on GPU tensors

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import _bin_classes as BC  # noqa: E402
 import _width_classes as WC  # noqa: E402
 from _decisions import saved_mult_check  # noqa: E402
 from _split_emul import check_rows, ideal_split_product, rows_at_exponents, split_host as _split_host  # noqa: E402
@@ -318,32 +319,76 @@ def test_linear_bwd_dw(m, k, j, affine):
     close("colsum", out, dy.double().sum(0), rtol=1e-6)
 
 
-@pytest.mark.parametrize("n,bins", [(1, 30), (10, 30), (33, 17), (70, 30), (257, 21), (515, 30)])      # >= 64 frames: the many-frame gradient kernels; >= 512: frame slices
-def test_audbl_conv1d(n, bins):
+def audbl_conv1d_case(n, bins):
+    """both Conv1d layers of AudBl chained, against float64 F.conv1d with autograd: forward (3e-6 of the tensor's max), weight, bias and
+    data gradients of both layers (1e-5), the data gradient of conv1 (d_audio) among them. Every output buffer starts as NaN.
+    The multi-launch form (relu_bwd + conv1d_bwd) runs at every row. Where goalnet_conv1d_bwd_small_ok serves a layer — the dispatch of
+    AVM.backward_device, layer by layer — the one-launch form runs too, is held to float64 at the same tolerances, and must equal the
+    multi-launch form as tests/test_gpu_small.py::test_conv1d_backward_in_one_launch_equals_the_multi_launch_form requires: the data
+    gradient bit for bit, weight and bias gradients (fp64 sums over the frames in another order) within 2e-6.
+    Returns the calls of (conv1d_bwd_small, conv1d_bwd) AVM's dispatch makes for the row."""
     x = rnd(n, 30, bins, seed=35, lo=-50, hi=50)
     w1 = rnd(64, 30, 3, seed=36, lo=-0.1, hi=0.1); b1 = rnd(64, seed=37)
     w2 = rnd(128, 64, 3, seed=38, lo=-0.07, hi=0.07); b2 = rnd(128, seed=39)
-    xd = x.double()
+    xd = x.double().requires_grad_(True)
     w1d, b1d, w2d, b2d = (t.double().requires_grad_(True) for t in (w1, b1, w2, b2))
     a1 = F.relu(F.conv1d(xd, w1d, b1d, stride=2, padding=1))
+    a1.retain_grad()
     a2 = F.relu(F.conv1d(a1, w2d, b2d, stride=2, padding=1))
     G = rnd(*a2.shape, seed=40).double()
     (a2 * G).sum().backward()
     l1, l2 = a1.shape[2], a2.shape[2]
-    xg = x.to(DEV)
-    g1 = torch.empty(n, 64, l1, device=DEV); g2 = torch.empty(n, 128, l2, device=DEV)
-    ops.conv1d_fwd(xg, w1.to(DEV), b1.to(DEV), g1, True, n, 30, bins, 64)
-    ops.conv1d_fwd(g1, w2.to(DEV), b2.to(DEV), g2, True, n, 64, l1, 128)
+    assert (l1, l2) == ((bins - 1) // 2 + 1, ((bins - 1) // 2) // 2 + 1)
+    xg, w1g, b1g, w2g, b2g, Gg = (t.to(DEV) for t in (x, w1, b1, w2, b2, G.float()))
+    g1 = _nan(n, 64, l1); g2 = _nan(n, 128, l2)
+    ops.conv1d_fwd(xg, w1g, b1g, g1, True, n, 30, bins, 64)
+    ops.conv1d_fwd(g1, w2g, b2g, g2, True, n, 64, l1, 128)
     close("audbl.conv1", g1, a1, rtol=3e-6); close("audbl.conv2", g2, a2, rtol=3e-6)
-    dz2 = torch.empty_like(g2)
-    ops.relu_bwd(G.float().to(DEV), g2, dz2)
-    da1 = torch.empty_like(g1); dw2 = torch.empty(128, 64, 3, device=DEV); db2 = torch.empty(128, device=DEV)
-    ops.conv1d_bwd(g1, dz2, w2.to(DEV), da1, dw2, db2, n, 64, l1, 128)
-    ops.relu_bwd(da1, g1, da1)
-    dw1 = torch.empty(64, 30, 3, device=DEV); db1 = torch.empty(64, device=DEV)
-    ops.conv1d_bwd(xg, da1, w1.to(DEV), None, dw1, db1, n, 30, bins, 64)
-    close("audbl.dw2", dw2, w2d.grad, rtol=1e-5); close("audbl.db2", db2, b2d.grad, rtol=1e-5)
-    close("audbl.dw1", dw1, w1d.grad, rtol=1e-5); close("audbl.db1", db1, b1d.grad, rtol=1e-5)
+
+    def against_fp64(tag, da1, dw2, db2, dx, dw1, db1):
+        close(f"audbl.dw2{tag}", dw2, w2d.grad, rtol=1e-5); close(f"audbl.db2{tag}", db2, b2d.grad, rtol=1e-5)
+        close(f"audbl.da1{tag}", da1, a1.grad, rtol=1e-5)
+        close(f"audbl.dw1{tag}", dw1, w1d.grad, rtol=1e-5); close(f"audbl.db1{tag}", db1, b1d.grad, rtol=1e-5)
+        close(f"audbl.d_audio{tag}", dx, xd.grad, rtol=1e-5)
+
+    # ---- multi-launch form: relu_bwd, conv1d_bwd (dx, dw, db), relu_bwd, conv1d_bwd
+    dz2 = ops.relu_bwd(Gg, g2, _nan(n, 128, l2))
+    da1 = _nan(n, 64, l1); dw2 = _nan(128, 64, 3); db2 = _nan(128)
+    ops.conv1d_bwd(g1, dz2, w2g, da1, dw2, db2, n, 64, l1, 128)
+    dz1 = ops.relu_bwd(da1, g1, _nan(n, 64, l1))
+    dx = _nan(n, 30, bins); dw1 = _nan(64, 30, 3); db1 = _nan(64)
+    ops.conv1d_bwd(xg, dz1, w1g, dx, dw1, db1, n, 30, bins, 64)
+    against_fp64("", da1, dw2, db2, dx, dw1, db1)
+    # the first layer needs no data gradient: dx = None leaves dw / db as they are
+    dw0 = _nan(64, 30, 3); db0 = _nan(64)
+    ops.conv1d_bwd(xg, dz1, w1g, None, dw0, db0, n, 30, bins, 64)
+    assert torch.equal(dw0, dw1) and torch.equal(db0, db1)
+
+    # ---- the dispatch of AVM.backward_device: per layer, one launch where the query says yes
+    ok2, ok1 = ops.conv1d_bwd_small_ok(n, 64, l1, 128), ops.conv1d_bwd_small_ok(n, 30, bins, 64)
+    ea1, ew2, eb2 = da1, dw2, db2
+    if ok2:
+        ea1 = _nan(n, 64, l1); ew2 = _nan(128, 64, 3); eb2 = _nan(128)
+        ops.conv1d_bwd_small(g1, Gg, g2, w2g, ea1, ew2, eb2, n, 64, l1, 128)
+        assert torch.equal(ea1, da1), "conv2's data gradient: one launch vs multi-launch (same 16-lane sums)"
+        close("conv1d_bwd_small.dw2", ew2, dw2, rtol=2e-6); close("conv1d_bwd_small.db2", eb2, db2, rtol=2e-6)
+    ex, ew1, eb1 = dx, dw1, db1
+    if ok1:
+        ex = _nan(n, 30, bins); ew1 = _nan(64, 30, 3); eb1 = _nan(64)
+        ops.conv1d_bwd_small(xg, ea1, g1, w1g, ex, ew1, eb1, n, 30, bins, 64)
+        assert torch.equal(ex, dx), "d_audio: one launch vs multi-launch (same 16-lane sums)"
+        close("conv1d_bwd_small.dw1", ew1, dw1, rtol=2e-6); close("conv1d_bwd_small.db1", eb1, db1, rtol=2e-6)
+        ew0 = _nan(64, 30, 3); eb0 = _nan(64)
+        ops.conv1d_bwd_small(xg, ea1, g1, w1g, None, ew0, eb0, n, 30, bins, 64)
+        assert torch.equal(ew0, ew1) and torch.equal(eb0, eb1)
+    if ok1 or ok2:
+        against_fp64(" (AVM's dispatch)", ea1, ew2, eb2, ex, ew1, eb1)
+    return int(ok1) + int(ok2), int(not ok1) + int(not ok2)
+
+
+@pytest.mark.parametrize("n,bins", BC.CONV1D_EXISTING)      # >= 64 frames: the many-frame gradient kernels; >= 512: frame slices
+def test_audbl_conv1d(n, bins):
+    audbl_conv1d_case(n, bins)
 
 
 @pytest.mark.parametrize("n", [1, 10, 300])

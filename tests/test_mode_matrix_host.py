@@ -9,6 +9,9 @@
     on the device either), never a measurement of the device;
   * DRY RUN of the runner's comparison: compare() accepts the oracle standing in for the device, and turns red when that stand-in ran
     on swapped frames, or in train mode for an eval cell;
+  * AUDIO BIN LENGTHS OTHER THAN 30 (BIN_CELLS): each cell lands in the class tests/_bin_classes.py states for it, compare() accepts the
+    oracle on it, and the cell's own criterion rejects an oracle run on audio reversed along the bin axis, on audbl.conv1.weight's
+    gradient and on the logits: the audio branch is 128 of the 640 fused features, and a cell that cannot see it proves nothing;
   * FRAMES WITH H != W (SHAPE_CELLS): the hand-written geometry table is the model's, compare() accepts the oracle on every cell (which
     also settles the conditions that depend on the oracle alone: CLASS_GAP on every row, judge()), and the fp32 train cell of every
     shape turns red on a stand-in that mixed H and W up."""
@@ -19,14 +22,15 @@ import torch
 
 import eval_ref
 from _golden import Golden
-from _mode_case import (CELLS, CLASS_GAP, GUARD_GRADS, SHAPE_CELLS, SHAPE_GEOMETRY, SHAPE_LAUNCHES, TOL16, Cell, cell_id, compare,
+import _bin_classes as BC
+from _mode_case import (BIN_CELLS, CELLS, CLASS_GAP, GUARD_GRADS, SHAPE_CELLS, SHAPE_GEOMETRY, SHAPE_LAUNCHES, TOL16, Cell, cell_id, compare,
                         fixture_of, grad_verdict, is_fp32, oracle_as_device, oracle_grads)
 from cvml_goalnet_amd import synth
 from oracle import avm_ref
 from test_eval_golden import EVAL_CASES_SMALL, golden_buffers, head_of
 
 LEVELS = {"precision": ("fp32", "bf16", "fp16"), "head": ("regression", "classifier"), "audio": (True, False),
-          "mode": ("train", "eval"), "n": (10, 32), "hw": ((40, 40),)}
+          "mode": ("train", "eval"), "n": (10, 32), "hw": ((40, 40),), "bins": (30,)}
 
 
 def test_committed_cells_cover_every_three_way_combination():
@@ -240,3 +244,40 @@ def test_comparison_rejects_a_device_that_mixed_height_and_width_up(cell):
     else:
         with pytest.raises(AssertionError):
             compare(cell, fx, oracle_as_device(cell, fx, vis=fx["vis"].flip(3)), log=_quiet)
+
+
+# ---- audio bin lengths other than 30 ------------------------------------------------------------------------------------------------
+def test_bin_cells_are_the_six_rows_and_leave_the_committed_ids_alone():
+    assert len(BIN_CELLS) == 6 == len(set(BIN_CELLS)) and not set(BIN_CELLS) & (set(CELLS) | set(SHAPE_CELLS))
+    assert all(c.audio and c.hw == (40, 40) and c.bins != 30 for c in BIN_CELLS)
+    assert all(c.bins == 30 for c in CELLS + SHAPE_CELLS)
+    assert [cell_id(c) for c in BIN_CELLS[:2]] == ["fp32-regression-audio-train-n10-b60", "fp32-regression-audio-train-n60-b60"]
+    assert cell_id(Cell("fp32", "regression", True, "train", 10)) == "fp32-regression-audio-train-n10"
+    for c, (_, classes) in zip(BIN_CELLS, BC.STEP_CELLS):
+        fx = fixture_of(c)
+        assert fx["aud"].shape == (c.n, 30, c.bins)
+        assert fx["p"]["audbl.linear3.weight"].shape == (128, 128 * classes["l2"])
+
+
+@pytest.mark.parametrize("cell", BIN_CELLS, ids=cell_id)
+def test_bin_cell_is_accepted_as_the_oracle_and_rejects_reversed_audio(cell):
+    """oracle vs oracle with the audio reversed along the bin axis, everything else fixed. The cell's own criterion must reject it on
+    audbl.conv1.weight's gradient and on the logits. Measured on the oracle alone ("every audio bin length")."""
+    fx = fixture_of(cell)
+    figures = compare(cell, fx, oracle_as_device(cell, fx), log=_quiet)
+    assert figures["disagree"] == 0
+    rev = dict(fx, aud=fx["aud"].flip(2).contiguous())
+    assert not torch.equal(rev["aud"], fx["aud"])
+    g, _ = oracle_grads(cell, fx)
+    gr, _ = oracle_grads(cell, rev)
+    g64 = oracle_grads(cell, fx, dtype=torch.float64)[0] if is_fp32(cell) else None
+    name = "audbl.conv1.weight"
+    fig, bad = grad_verdict(cell, name, gr[name], g[name], None if g64 is None else g64[name])
+    honest, wrong = oracle_as_device(cell, fx), oracle_as_device(cell, rev)
+    e_logit = (wrong["logit"] - honest["logit"]).abs().max().item()
+    tol = 2e-5 if is_fp32(cell) else TOL16[cell.precision][0]
+    print(f"[matrix] {cell_id(cell)} reversed audio: {name} {fig:.3e}; logits {e_logit:.3e} (tolerance {tol})")
+    assert bad is not None, f"{name}: the cell's criterion accepts reversed audio ({fig:.3e})"
+    assert e_logit > tol, f"the cell's logit tolerance accepts reversed audio ({e_logit:.3e} <= {tol})"
+    with pytest.raises(AssertionError):
+        compare(cell, fx, wrong, log=_quiet)

@@ -12,12 +12,12 @@ from _golden import GOLDEN_CASES_SMALL, Golden
 def test_oracle_matches_reference_goldens(case):
     g = Golden(case)
     torch.set_num_threads(8)
-    params = synth.make_params(g.h, g.h, 30, g.audio)
+    params = synth.make_params(g.h, g.h, g.bins, g.audio)
     p = {k: torch.from_numpy(v.copy()) for k, v in params.items()}
     b = avm_ref.init_buffers()
     state = {}
     vis = torch.from_numpy(synth.make_visual(g.n, g.h, g.h))
-    aud = torch.from_numpy(synth.make_audio(g.n)) if g.audio else None
+    aud = torch.from_numpy(synth.make_audio(g.n, g.bins)) if g.audio else None
     lab = torch.from_numpy(synth.make_labels(g.n))
     for s in range(g.steps):
         masks = [torch.from_numpy(m) for m in synth.make_drop_masks(g.n, step=s)] if g.drop else None

@@ -234,6 +234,12 @@ EMA_PROTOTYPES = {
     "goalnet_swap_ranges": (c_int, [P, P, ctypes.POINTER(AdamRange), c_int, P]),
 }
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_accum.h, the sixth public header (gradient
+# accumulation over the sub-batches of a window): additions, the tables above stay as they are
+ACCUM_PROTOTYPES = {
+    "goalnet_grad_accum_dev_ranges": (c_int, [P, P, ctypes.POINTER(AdamRange), c_int, c_float, c_int, P]),
+}
+
 _lib = None
 
 
@@ -252,7 +258,7 @@ def load():
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
-                              *EMA_PROTOTYPES.items()):
+                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

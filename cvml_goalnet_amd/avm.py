@@ -248,6 +248,30 @@ def ema_step_path(ema, *, sharded):
     return True
 
 
+def accum_count(k):
+    """train_step's / VideoTrainer's `accumulate` -> the window length as an int >= 1; anything else — a bool, a
+    float, 0 — is a ValueError. Pure: the host tests call it."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"accumulate must be an integer >= 1, got {k!r}")
+    return k
+
+
+def accum_windows(n_frames, subbatch_size, k):
+    """[(rows, position, length)] per sub-batch of a video of n_frames: how loop.VideoTrainer(accumulate=k) cuts the video's sub-batches
+    (main.py:177-184: subbatch_size frames each, a shorter last one) into windows of k micro-steps. Windows never span videos: the last
+    window may be shorter, length j < k, and runs as a window of j (c = 1 / j), applied at the end of the video. Pure: the host tests
+    call it."""
+    k = accum_count(k)
+    if n_frames < 1 or subbatch_size < 1:
+        raise ValueError("n_frames and subbatch_size must be >= 1")
+    rows = [min(subbatch_size, n_frames - off) for off in range(0, n_frames, subbatch_size)]
+    out = []
+    for s, r in enumerate(rows):
+        start = s - s % k
+        out.append((r, s - start, min(k, len(rows) - start)))
+    return out
+
+
 STATE_FORMAT = 1               # AVM.training_state()["format"]
 
 
@@ -354,6 +378,11 @@ class AVM(_LazyFlags, nn.Module):
         # that is given ema=; _averaged: inside `with model.averaged()` the two arenas are exchanged
         self._ema = None
         self._averaged = False
+        # gradient accumulation: a second gradient arena, allocated by the first train_step(accumulate=k > 1); the
+        # position in the window is HOST state — (micro-steps done, k) and the frozen set the window started under
+        self._gacc = None
+        self._accum_done, self._accum_k, self._accum_frozen = 0, 1, None
+        self._norm_of_acc = False      # grad_norm() reads the accumulated gradient: the last backward was an accumulating train_step's
         self._state = None             # int64[4] device counters: adam step, dropout draw, frame cursor, sub-batch index
         self._materialized = False
         self.grad_sync = None          # optional ddp.GradSync: gradient exchange between backward and Adam
@@ -1203,6 +1232,8 @@ class AVM(_LazyFlags, nn.Module):
         if params:
             self._ensure_garena()
             self._bwd_frozen = frozen
+            if self._norm_of_acc:
+                self._norm_of_acc = False
         dev = self._device
         n, h, w = ctx["n"], ctx["h"], ctx["w"]
         # small steps: weight / bias gradients and the AudBl branch run on a side stream under the dX chain (_Fork)
@@ -1487,8 +1518,15 @@ class AVM(_LazyFlags, nn.Module):
     # device-resident fused train step: forward, broadcast MSE, backward, Adam
     # ------------------------------------------------------------------------------------------
     def train_step(self, audio, visual, labels, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, _loop_tick=(0, 0), _scatter=None, *,
-                   loss="mse_bcast", loss_param=None, weights=None, optim=None, ema=None):
+                   loss="mse_bcast", loss_param=None, weights=None, optim=None, ema=None, accumulate=1):
         """main.py:187-193 on GPU tensors. Returns (loss (1,), pred (N,)) as GPU tensors, no host sync.
+        `accumulate` (EXTENSION): k >= 1 — one optimizer step per WINDOW of k calls. Every call is a micro-step: forward,
+        loss, backward into the gradient arena, scatter and the counters' tick as ever, then ONE launch adds gradient / k into the
+        arena `_gacc` (accum_of; the window's first call overwrites it). Only the window's last call updates — the same launches, reading
+        `_gacc` with grad_scale 1 — and moves the average and the step counter: schedules, the average and the bias corrections count
+        windows, the clipping norm is the accumulated gradient's. 1: exactly the step without the argument, no arena. k > 1 switches the
+        early Adam and the epilogue-fused update off (as `optim` does), refuses precision="fp16" and an attached grad_sync / stat_sync,
+        and k and the frozen set may not change inside a window (accum_position).
         `optim` (EXTENSION): optim.OptimOptions — weight decay, gradient-norm clipping, a learning-rate schedule on
         `lr`. None or trivial options: exactly the step without the argument. Otherwise the update is one launch after backward
         (optim_step_path): no early Adam, no update in linear5's weight-gradient epilogue.
@@ -1507,6 +1545,8 @@ class AVM(_LazyFlags, nn.Module):
         grad_of("visbl.linear5.weight") returns whatever an earlier backward left there. keep_ctx = True or epi_fuse = False keep it."""
         loss_kind = loss
         ops.loss_spec(loss_kind, loss_param, weights is not None, self.head)       # ValueError before anything is launched
+        k = accum_count(accumulate)
+        self._check_accumulate(k)                       # GoalnetError before anything is launched
         opt_on = optim_step_path(optim, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
         ema_on = ema_step_path(ema, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
         self._refuse_averaged("train_step")
@@ -1571,9 +1611,11 @@ class AVM(_LazyFlags, nn.Module):
         fuse5 = epi_fuse_dw_adam(n, plain=plain, synced=sync is not None, precision=self.precision,
                                  train_w5="visbl.linear5.weight" not in frozen, shadowed=self._w5b is not None, inspected=self.keep_ctx,
                                  forced=self.epi_fuse, pieces=epi_fuse_pieces(os.environ.get("GOALNET_F32_EPI_FUSE")))
-        if opt_on:
-            fuse5 = False                                 # both shortcuts hard-code plain Adam, and clipping needs the whole norm first
-        early = early and not fuse5 and not opt_on
+        if opt_on or k > 1:
+            # both shortcuts hard-code plain Adam on this step's own gradient; clipping needs the whole norm first, and a window
+            # updates from the accumulated gradient, on its last micro-step only
+            fuse5 = False
+        early = early and not fuse5 and not opt_on and k == 1
         # (small steps: the same update as a background pass on a third stream was measured slower at every width)
         done_early = []
 
@@ -1621,16 +1663,84 @@ class AVM(_LazyFlags, nn.Module):
             guard = self._guard[0]
         # (the early Adam ran on the side stream: backward_device's last act joins it into this stream, so the average, issued by
         # adam_step behind its own launches, reads every updated weight)
-        self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early, optim=optim if opt_on else None, ema=ema)
+        d0 = 1                                            # what the step counter state[0] advances by
+        if k == 1:
+            self.adam_step(lr, betas, eps, scale / lscale, _tick=False, _guard=guard, _done=done_early, optim=optim if opt_on else None, ema=ema)
+        else:
+            # a micro-step of a window: gradient / k into the accumulator behind the backward (no exchange and no loss scale here: both
+            # are refused above), and on the window's last micro-step the update from the accumulator
+            first, last = self._accum_done == 0, self._accum_done == k - 1
+            ranges = trainable_ranges(self._specs, frozen, {})
+            if len(ranges) > ops.ADAM_RANGES_MAX:
+                raise GoalnetError(f"{len(ranges)} trainable ranges: the accumulation pass takes {ops.ADAM_RANGES_MAX}")
+            if self._gacc is None:
+                self._gacc = torch.zeros(self._arena_numel, dtype=F32, device=self._device)
+            if ranges:
+                ops.grad_accum_dev_ranges(self._gacc, self._garena, ranges, 1.0 / k, first)
+            self._norm_of_acc = True
+            if last:
+                self.adam_step(lr, betas, eps, 1.0, _tick=False, optim=optim if opt_on else None, ema=ema, _grads=self._gacc)
+            else:
+                d0 = 0
+            self._accum_advance(k, frozen)
         if _scatter is not None:
-            ops.rows_scatter_tick(_scatter(loss, out), self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], bad_step=guard)
+            ops.rows_scatter_tick(_scatter(loss, out), self._state, d0, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], bad_step=guard)
         elif guard is not None:
             # a step whose Adam was skipped is not counted (torch's GradScaler does not count it either): the retry runs under
             # the same step count; `_adam_t` on the host counts ATTEMPTED steps
             ops.counters_add4_guarded(self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1], guard)
         else:
-            ops.counters_add4(self._state, 1, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1])
+            ops.counters_add4(self._state, d0, ctx["drop_ticks"], _loop_tick[0], _loop_tick[1])
         return loss, out
+
+    # ------------------------------------------------------------------------------------------
+    # gradient accumulation
+    # ------------------------------------------------------------------------------------------
+    @property
+    def accum_position(self):
+        """(micro-steps of the current window done so far, the window's k); (0, k) between windows"""
+        return self._accum_done, self._accum_k
+
+    def _check_accumulate(self, k):
+        """train_step(accumulate=k)'s refusals, all before anything is launched or allocated"""
+        if self._accum_done:
+            if k != self._accum_k:
+                raise GoalnetError(f"accumulate changed from {self._accum_k} to {k} after {self._accum_done} micro-step(s) of a window: "
+                                   "k may not change inside a window")
+            if self._frozen_names() != self._accum_frozen:
+                raise GoalnetError("the set of frozen tensors changed inside an accumulation window: the accumulator holds the "
+                                   "gradients of the set the window started under")
+        if k == 1:
+            return
+        if self.precision == "fp16":
+            raise GoalnetError("accumulate > 1 with precision='fp16' is not built: the overflow guard's skipped steps and the loss scale "
+                               "would have to act on a whole window (DESIGN.md §4.16)")
+        if self.grad_sync is not None or self.stat_sync is not None:
+            raise GoalnetError("accumulate > 1 with a grad_sync / stat_sync attached is not built: the exchange would have to be "
+                               "skipped on a window's non-final micro-steps (DESIGN.md §4.16)")
+
+    def _accum_advance(self, k, frozen):
+        """the host's view of one micro-step of a window of k (train_step, and loop.VideoTrainer after a replay)"""
+        self._accum_k, self._accum_frozen = k, frozenset(frozen)
+        self._accum_done = (self._accum_done + 1) % k
+        self._norm_of_acc = True
+
+    def _refuse_mid_window(self, what):
+        if self._accum_done:
+            raise GoalnetError(f"{what} after {self._accum_done} of {self._accum_k} micro-steps of an accumulation window: "
+                               "finish the window first")
+
+    def accum_of(self, name) -> Optional[torch.Tensor]:
+        """The accumulated gradient of a parameter — sum over the window's micro-steps so far of gradient / k — as a view with the
+        reference's logical shape, like grad_of (which keeps showing the last micro-step's own gradient); None for a tensor that is
+        frozen in this window."""
+        if self._gacc is None:
+            raise GoalnetError("no accumulated gradient yet: pass accumulate=k > 1 to train_step / VideoTrainer first")
+        if self._accum_frozen is not None and name in self._accum_frozen:
+            return None
+        s = self.spec(name)
+        v = self._view(self._gacc, s)
+        return v.reshape(s.shape[0], -1) if s.kind == "lin5" else v
 
     def _adam_segments(self):
         """[(lo, hi)] arena ranges this rank's optimizer owns: everything, or — ddp.GradSync(shard_linear5=True) — everything
@@ -1676,13 +1786,13 @@ class AVM(_LazyFlags, nn.Module):
             self._adam_segs = segs
         return segs
 
-    def _adam_piece(self, lo, hi, moff, lr, betas, eps, grad_scale, guard=None):
+    def _adam_piece(self, lo, hi, moff, lr, betas, eps, grad_scale, guard=None, grads=None):
         """the fused Adam on arena[lo:hi] against the moments at [moff, moff + hi - lo) (moff = lo unless the optimizer state is sharded).
         Refreshes the part of the valid 16-bit copy of linear5.weight that lies inside, in the same pass (the kernels do not bump
         versions). `guard` (fp16): the pass is skipped as a whole when this step's gradients overflowed (goalnet_grad_finite_check).
         The step counter is NOT advanced."""
         s5 = self.spec("visbl.linear5.weight")
-        p, g = self._arena[lo:hi], self._garena[lo:hi]
+        p, g = self._arena[lo:hi], (self._garena if grads is None else grads)[lo:hi]      # grads: the accumulator (DESIGN.md §4.16)
         m, v = self._adam_m[moff:moff + hi - lo], self._adam_v[moff:moff + hi - lo]
         a, b = max(lo, s5.offset), min(hi, s5.offset + s5.numel)       # the part of linear5.weight inside this piece
         sh = None
@@ -1696,13 +1806,15 @@ class AVM(_LazyFlags, nn.Module):
         else:
             ops.adam_step_dev(p, g, m, v, lr, betas[0], betas[1], eps, self._state[0], grad_scale, step_bias=1)
 
-    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, _tick=True, _guard=None, _done=(), optim=None, ema=None):
+    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, _tick=True, _guard=None, _done=(), optim=None, ema=None,
+                  _grads=None):
         """torch.optim.Adam defaults over the whole arena in one launch (main.py:70, 193). The step count is the device
         counter state[0] (= completed steps) + 1, so the same captured launch serves every step. With a sharded
         linear5.weight (ddp.py) the pass covers this rank's slice only — three launches — and the optimizer state exists
         only for what the rank owns. `optim` (optim.OptimOptions): non-trivial options run _optim_step instead.
         `ema` (optim.EmaOptions): behind the update, and in front of the launch that advances the step counter, one
-        launch folds the updated weights into the average (_ema_update)."""
+        launch folds the updated weights into the average (_ema_update). `_grads`: the arena the update reads in place of the gradient
+        arena (train_step's accumulator on a window's last micro-step)."""
         opt_on = optim_step_path(optim, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
         ema_on = ema_step_path(ema, sharded=bool(getattr(self.grad_sync, "shard_linear5", False)))
         self._refuse_averaged("adam_step")
@@ -1718,7 +1830,7 @@ class AVM(_LazyFlags, nn.Module):
                 raise GoalnetError("precision='fp16': the set of frozen tensors may not change after the first optimizer step")
         if opt_on:
             assert not _done
-            return self._optim_step(lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema if ema_on else None)
+            return self._optim_step(lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema if ema_on else None, _grads)
         segs = self._adam_state()
         self._adam_t += 1
         if not self._plain_step(frozen):
@@ -1731,8 +1843,9 @@ class AVM(_LazyFlags, nn.Module):
             s5 = self.spec("visbl.linear5.weight")
             shadow = self._w5b if (s5.name not in frozen and self._w5b is not None and self._w5b_version == self._w5_version()) else None
             if ranges:
-                ops.adam_step_dev_ranges(self._arena, self._garena, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps,
-                                         self._state[0], grad_scale, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
+                ops.adam_step_dev_ranges(self._arena, self._garena if _grads is None else _grads, self._adam_m, self._adam_v, ranges, lr,
+                                         betas[0], betas[1], eps, self._state[0], grad_scale, shadow=shadow, shadow_begin=s5.offset,
+                                         bad_step=_guard)
             self._count_sat_out(frozen)
             if ema_on:
                 self._ema_update(ema, frozen, _guard)
@@ -1752,7 +1865,7 @@ class AVM(_LazyFlags, nn.Module):
                 pieces.append((lo, hi, off))
                 off += hi - lo
         for lo, hi, moff in pieces:
-            self._adam_piece(lo, hi, moff, lr, betas, eps, grad_scale, _guard)
+            self._adam_piece(lo, hi, moff, lr, betas, eps, grad_scale, _guard, _grads)
         if len(segs) > 1:
             shadow_ok = self._w5b is not None and self._w5b_version == self._w5_version()
             self.grad_sync.after_adam(self, self._w5b if shadow_ok else None)
@@ -1761,7 +1874,7 @@ class AVM(_LazyFlags, nn.Module):
         if _tick:
             ops.counter_add(self._state[0], 1)
 
-    def _optim_step(self, lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema=None):
+    def _optim_step(self, lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema=None, grads=None):
         """adam_step under non-trivial options: the squared norm of the trainable gradients (clipping only; after the gradient exchange,
         so grad_scale carries 1 / world) and ONE launch over the trainable ranges, split where the decay flag changes. The learning
         rate is the schedule's at the device step counter; 16-bit copy and fp16 guard pass through as in _adam_piece."""
@@ -1773,9 +1886,10 @@ class AVM(_LazyFlags, nn.Module):
         self._adam_t += 1
         s5 = self.spec("visbl.linear5.weight")
         shadow = self._w5b if (s5.name not in frozen and self._w5b is not None and self._w5b_version == self._w5_version()) else None
+        g = self._garena if grads is None else grads
         if ranges:
-            sumsq = ops.grad_sumsq(self._garena, ranges) if optim.max_grad_norm is not None else None
-            ops.optim_step_dev_ranges(self._arena, self._garena, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps, optim,
+            sumsq = ops.grad_sumsq(g, ranges) if optim.max_grad_norm is not None else None
+            ops.optim_step_dev_ranges(self._arena, g, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps, optim,
                                       self._state[0], grad_scale, sumsq=sumsq, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
         self._count_sat_out(frozen)
         if ema is not None:
@@ -1831,6 +1945,7 @@ class AVM(_LazyFlags, nn.Module):
         does a nested entry."""
         if self._averaged:
             raise GoalnetError("model.averaged() is already active: the block does not nest")
+        self._refuse_mid_window("model.averaged()")
         if self._ema is None:
             raise GoalnetError("no weight average yet: pass ema=EmaOptions(...) to train_step / adam_step / VideoTrainer first")
         if self.grad_sync is not None and getattr(self.grad_sync, "shard_linear5", False):
@@ -1866,6 +1981,7 @@ class AVM(_LazyFlags, nn.Module):
         host synchronisation."""
         self._refuse_sharded_state("training_state()")
         self._refuse_averaged("training_state()")
+        self._refuse_mid_window("training_state()")
         if not self._materialized:
             raise RuntimeError("training_state() before the first forward / load_state_dict(): parameters are uninitialised")
         if self._state is None:
@@ -1896,6 +2012,7 @@ class AVM(_LazyFlags, nn.Module):
         dropout_mode "given" is not restored (its masks are not part of the state): the model's own mode stays."""
         self._refuse_sharded_state("load_training_state()")
         self._refuse_averaged("load_training_state()")
+        self._refuse_mid_window("load_training_state()")
         if not isinstance(state, dict) or state.get("format") != STATE_FORMAT:
             raise RuntimeError(f"load_training_state: not a training state of format {STATE_FORMAT}")
         mine = self._identity()
@@ -1939,7 +2056,8 @@ class AVM(_LazyFlags, nn.Module):
         """(1,) float64 on the device, no sync: the L2 norm of the gradients of the tensors that trained in the last backward, as the
         gradient arena holds them (ops.grad_sumsq over the trainable ranges), divided by the loss scale an fp16 train_step left in
         the arena. What max_grad_norm is compared with. After a step that updated linear5.weight in its weight-gradient epilogue
-        (train_step's docstring) that tensor's slot holds an earlier backward's gradient."""
+        (train_step's docstring) that tensor's slot holds an earlier backward's gradient. After a train_step(accumulate=k > 1) it is the
+        norm of the ACCUMULATED gradient (accum_of), which is what that window's clipping compares."""
         if self._garena is None:
             raise RuntimeError("grad_norm() before any backward: there are no gradients")
         ranges = [(b, c, k, False) for b, c, k in trainable_ranges(self._specs, self._bwd_frozen, self._sat_out)]
@@ -1947,7 +2065,7 @@ class AVM(_LazyFlags, nn.Module):
             return torch.zeros(1, dtype=torch.float64, device=self._device)
         if len(ranges) > ops.ADAM_RANGES_MAX:
             raise GoalnetError(f"{len(ranges)} trainable ranges: one launch takes {ops.ADAM_RANGES_MAX}")
-        norm = ops.grad_sumsq(self._garena, ranges).sqrt_()
+        norm = ops.grad_sumsq(self._gacc if self._norm_of_acc else self._garena, ranges).sqrt_()
         return norm / self._arena_grad_scale if self._arena_grad_scale != 1.0 else norm
 
     def current_lr(self, lr=1e-3, optim=None) -> float:

@@ -35,6 +35,11 @@ sub-batch's optimizer step (`AVM.train_step(ema=)`, one more launch inside the s
 `state_dict()` / `load_state_dict()` save and restore the run — the model's training state and the trainer's pass index — so that a
 resumed run continues bit for bit.
 
+EXTENSION (off by default): `accumulate=k` applies one optimizer step per window of k sub-batches
+(`AVM.train_step(accumulate=)`): every sub-batch is a micro-step whose gradient / k is added into a second arena, and the window's last
+one updates from it. Windows never span videos: a video's last window may be shorter (j < k sub-batches, run as a window of j) and is
+applied at the end of the video (`accum_windows`). The graph key carries the phase (first?, last?, length).
+
 EXTENSION (off by default): `shuffle=True` / `augment={...}` draw a plan per pass on the device — frame order, flip,
 shift, contrast, brightness per frame — and the same graphs gather their sub-batches through it; predictions come back in frame order.
 """
@@ -45,6 +50,7 @@ from typing import Dict, Tuple
 import torch
 
 from . import augment as _augment, ops, synth
+from .avm import accum_count, accum_windows
 from .optim import EmaOptions, OptimOptions
 
 TRAINER_STATE_FORMAT = 1
@@ -60,9 +66,12 @@ def _plain(x):
 class VideoTrainer:
     def __init__(self, model, subbatch_size: int = 10, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  graphs: bool = True, loss: str = "mse_bcast", loss_param=None, shuffle: bool = False, augment=None,
-                 seed: int = synth.BASE_SEED, optim=None, ema=None):
+                 seed: int = synth.BASE_SEED, optim=None, ema=None, accumulate: int = 1):
         if subbatch_size < 1:
             raise ValueError("subbatch_size must be >= 1")
+        # EXTENSION: sub-batches per optimizer step. 1: train_step is called as before.
+        self.accumulate = accum_count(accumulate)
+        self._phase = (True, True, 1)               # (first?, last?, length) of the micro-step _sub_step is about to issue
         if optim is not None and not isinstance(optim, OptimOptions):
             raise ValueError("optim must be an optim.OptimOptions")
         # EXTENSION: optimizer options of every sub-batch's step. None / trivial: train_step is called as before.
@@ -92,7 +101,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, ema signature, training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, ema signature, accumulation phase, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -126,6 +135,11 @@ class VideoTrainer:
         # the pass plan (augment.py): rewritten eagerly by every train_video, read by the graphs at this address
         self._plan = torch.zeros(cap, 8, dtype=torch.int32, device=dev) if self._planned else None
 
+    def _step_kw(self):
+        """train_step's keyword arguments beyond the loss: optimizer options, weight average, and — inside a window of more than one
+        micro-step — the window's length"""
+        return self._okw if self._phase[2] == 1 else dict(self._okw, accumulate=self._phase[2])
+
     def _sub_step(self, n: int):
         """gather rows -> train_step -> scatter results -> advance the counters. Pure device work (capturable)."""
         m = self.model
@@ -151,7 +165,7 @@ class VideoTrainer:
         ops.rows_copy_batch(segs)                                       # frames[a:b], labels[a:b], audios[a:b], weights[a:b]
         # train_step advances all four counters in its last launch: cursor += n, sub-batch index += 1
         if m.head == "classifier":
-            loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **self._okw)
+            loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **self._step_kw())
             pred = ops.argmax_plus1(pred, torch.empty(n, dtype=F32, device=dev))        # main.py:190: argmax + 1 is what gets collected
             # predictions.extend(...), losses.append(...) at the positions the step started from
             ops.rows_copy_batch([(self._pred, pred, n, st[2], -n, False), (self._loss, loss, 1, st[3], -1, False)])
@@ -159,7 +173,7 @@ class VideoTrainer:
         # regression head: that same last launch first writes predictions.extend(...), losses.append(...) at the positions the step
         # started from (main.py:195-196), then moves the counters
         m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1),
-                     _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)], **lkw, **self._okw)
+                     _scatter=lambda loss, pred: [(self._pred, pred, n, st[2], 0, False), (self._loss, loss, 1, st[3], 0, False)], **lkw, **self._step_kw())
 
     def _sub_step_planned(self, n: int, vis, lab):
         """_sub_step with the sub-batch taken through the pass plan: frames plan[cursor : cursor + n] in that order, augmented as their
@@ -182,7 +196,7 @@ class VideoTrainer:
             lkw = dict(loss=self.loss, loss_param=self.loss_param, weights=wts)
         ops.rows_copy_indexed(segs, self._plan)
         # the step's last launch moves the counters; the results are then written at the positions the step started from
-        loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **lkw, **self._okw)
+        loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **lkw, **self._step_kw())
         if m.head == "classifier":
             pred = ops.argmax_plus1(pred, torch.empty(n, dtype=F32, device=dev))        # main.py:190
         ops.rows_copy_indexed([(self._pred, pred, n, st[2], -n, False, True), (self._loss, loss, 1, st[3], -1, False, False)], self._plan)
@@ -190,8 +204,13 @@ class VideoTrainer:
     def _host_bookkeeping_after_replay(self):
         """What an eager train_step does on the host besides launching kernels."""
         m = self.model
-        m._adam_t += 1
-        m._count_sat_out(m._bwd_frozen)             # the replayed optimizer step: one more that the frozen tensors sat out
+        if self._phase[2] > 1:
+            m._accum_advance(self._phase[2], m._bwd_frozen)     # one more micro-step of the window
+        elif m._norm_of_acc:
+            m._norm_of_acc = False
+        if self._phase[1]:                          # a window's last micro-step (every step, without accumulation) updates
+            m._adam_t += 1
+            m._count_sat_out(m._bwd_frozen)         # the replayed optimizer step: one more that the frozen tensors sat out
         if not m.training:
             return                                  # eval(): no dropout draw, BatchNorm buffers untouched
         if m.dropout_mode == "device":
@@ -217,8 +236,10 @@ class VideoTrainer:
         # () without options. The schedule itself advances inside replays: it reads the device step counter.
         # The weight average's constants are launch arguments too, and its arena's address is baked in: its signature is k[6], ()
         # when off. Which steps copy, average or pass is decided inside replays, from the device step counter.
+        # Accumulation: whether the micro-step overwrites or adds to the accumulator, whether it updates, and 1 / length
+        # are baked into the launches, so the phase (first?, last?, length) is k[7]; (True, True, 1) without accumulation.
         gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted),
-                (self.shuffle, self._colour, self._augments), self._optim_sig, self._ema_sig, m.training)
+                (self.shuffle, self._colour, self._augments), self._optim_sig, self._ema_sig, self._phase, m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -242,6 +263,7 @@ class VideoTrainer:
                 return
             saved = (m._adam_t, m._drop_step, [int(getattr(m.visbl, f"bnorm{i}").num_batches_tracked) for i in (1, 2, 3)],
                      m.keep_ctx)
+            window = (m._accum_done, m._accum_k, m._accum_frozen)
             sat_out = dict(m._sat_out)
             m.keep_ctx = False
             g = torch.cuda.CUDAGraph()
@@ -253,6 +275,7 @@ class VideoTrainer:
             # capturing launched nothing: undo the host-side counters the captured code advanced
             m._adam_t, m._drop_step, nbt, m.keep_ctx = saved
             m._sat_out = sat_out
+            m._accum_done, m._accum_k, m._accum_frozen = window
             for i, v in zip((1, 2, 3), nbt):
                 getattr(m.visbl, f"bnorm{i}").num_batches_tracked.fill_(v)
             self._graphs[gkey] = g
@@ -264,7 +287,10 @@ class VideoTrainer:
 
     # ---- exact save / resume --------------------------------------------------------------------------
     def _signatures(self):
-        return {"loss": (self.loss, self.loss_param), "plan": (self.shuffle, tuple(sorted(self.augment.items()))),
+        # (windows end with the video, so a state taken between two videos needs nothing about them; "accumulate" is listed only when
+        # on, which keeps a default trainer's state what it was)
+        acc = {} if self.accumulate == 1 else {"accumulate": self.accumulate}
+        return {**acc, "loss": (self.loss, self.loss_param), "plan": (self.shuffle, tuple(sorted(self.augment.items()))),
                 "optim": self._optim_sig, "ema": self._ema_sig, "subbatch_size": self.subbatch_size,
                 "step": (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps))}
 
@@ -367,9 +393,9 @@ class VideoTrainer:
             # the previous video's results have been read back by now (main.py:203): a cheap place to notice skipped steps and
             # halve the loss scale (AVM.update_loss_scale) — a static scale would otherwise stall training silently
             m.update_loss_scale()
-        sb = self.subbatch_size
         subs = 0
-        for off in range(0, n_frames, sb):
-            self._run(min(sb, n_frames - off))
+        for rows, pos, length in accum_windows(n_frames, self.subbatch_size, self.accumulate):
+            self._phase = (pos == 0, pos == length - 1, length)
+            self._run(rows)
             subs += 1
         return self._loss[:subs].clone(), self._pred[:n_frames].clone()

@@ -1107,6 +1107,19 @@ def swap_ranges(a, b, ranges):
     check(lib().goalnet_swap_ranges(a.data_ptr(), b.data_ptr(), arr, len(ranges), _s()), "swap_ranges")
 
 
+# ---- gradient accumulation over a window of micro-steps (include/goalnet_accum.h) ----
+def grad_accum_dev_ranges(acc, g, ranges, scale, first):
+    """acc = g * scale (`first`: acc is not read) or acc = acc + g * scale over `ranges` in ONE launch; the product and the sum are
+    rounded separately in fp32, as the two torch operations `t = g * scale; acc + t` are."""
+    _chk(acc, g)
+    n = g.numel()
+    _req(acc.dtype == F32 and g.dtype == F32 and acc.is_contiguous() and g.is_contiguous() and acc.numel() == n,
+         "grad_accum_dev_ranges: acc and g must be contiguous fp32 arenas of one size")
+    arr = _plain_ranges("grad_accum_dev_ranges", ranges, n)
+    check(lib().goalnet_grad_accum_dev_ranges(acc.data_ptr(), g.data_ptr(), arr, len(ranges), float(scale), int(bool(first)), _s()),
+          "grad_accum_dev_ranges")
+
+
 def scale_(x, s):
     _chk(x)
     _req(x.dtype == F32 and x.is_contiguous(), "scale_: argument check failed: x.dtype == F32 and x.is_contiguous()")

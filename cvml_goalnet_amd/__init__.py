@@ -12,12 +12,12 @@ from . import synth  # noqa: F401
 from ._lib import GoalnetError, LIB_PATH  # noqa: F401
 from .avm import AVM  # noqa: F401
 from . import optim  # noqa: F401
-from .optim import EmaOptions, OptimOptions  # noqa: F401
+from .optim import EmaOptions, OptimOptions, ParamGroup  # noqa: F401
 from .summarize import VideoSummarizer, VideoSummary  # noqa: F401
 from . import groundtruth  # noqa: F401
 from .segment import Segmentation, TemporalSegmenter  # noqa: F401
 from .rankcorr import HumanConsistency, RankCorrelation, RankEvaluator, rank_correlation  # noqa: F401
 from .augment import epoch_plan, gather_augmented  # noqa: F401
 
-__all__ = ["epoch_plan", "gather_augmented","AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "OptimOptions", "EmaOptions","VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
+__all__ = ["epoch_plan", "gather_augmented","AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "OptimOptions", "ParamGroup", "EmaOptions","VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
            "Segmentation", "RankEvaluator", "RankCorrelation", "HumanConsistency", "rank_correlation"]

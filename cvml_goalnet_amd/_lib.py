@@ -48,6 +48,17 @@ class OptimOpts(ctypes.Structure):
                 ("period", c_int64), ("decoupled", c_int32), ("schedule", c_int32)]
 
 
+class GroupHyper(ctypes.Structure):
+    """goalnet_group_hyper (include/goalnet_groups.h)"""
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
+                ("amsgrad", c_int32), ("pad", c_int32)]
+
+
+class GroupRange(ctypes.Structure):
+    """goalnet_group_range (include/goalnet_groups.h)"""
+    _fields_ = [("begin", c_int64), ("count", c_int64), ("skipped", c_int64), ("decay", c_int32), ("group", c_int32)]
+
+
 class EmaOpts(ctypes.Structure):
     """goalnet_ema_opts (include/goalnet_ema.h)"""
     _fields_ = [("decay", c_double), ("every", c_int64), ("start_step", c_int64), ("warmup", c_int32), ("pad", c_int32)]
@@ -240,6 +251,15 @@ ACCUM_PROTOTYPES = {
     "goalnet_grad_accum_dev_ranges": (c_int, [P, P, ctypes.POINTER(AdamRange), c_int, c_float, c_int, P]),
 }
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_groups.h, the seventh public header (parameter
+# groups and AMSGrad on the fused step): additions, the tables above stay as they are
+GROUPS_PROTOTYPES = {
+    "goalnet_group_step_dev_ranges": (c_int, [P, P, P, P, P, ctypes.POINTER(GroupRange), c_int, ctypes.POINTER(GroupHyper), c_int,
+                                              ctypes.POINTER(OptimOpts), P, c_float, P, P, c_int64, c_int64, c_int, P, P]),
+    "goalnet_group_lr": (c_int, [ctypes.POINTER(OptimOpts), ctypes.POINTER(GroupHyper), c_int, P, P, P]),
+}
+GROUPS_MAX = 8            # GOALNET_GROUPS_MAX
+
 _lib = None
 
 
@@ -258,7 +278,7 @@ def load():
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
-                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items()):
+                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

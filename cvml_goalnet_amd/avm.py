@@ -227,7 +227,7 @@ def optim_step_path(optim, *, sharded):
     if optim is None or optim.trivial:
         return False
     if sharded:
-        raise GoalnetError("optimizer options (weight decay, clipping, schedules) are not built for ddp.GradSync(shard_linear5=True): "
+        raise GoalnetError("optimizer options (weight decay, clipping, schedules, parameter groups, AMSGrad) are not built for ddp.GradSync(shard_linear5=True): "
                            "a rank holds only its slice of linear5.weight's gradient; use a plain GradSync")
     return True
 
@@ -291,6 +291,28 @@ def optim_ranges(specs, frozen, skipped, optim):
             out.append((s.offset, s.numel, k, d))
         slot_end = s.offset + (s.numel + _ALIGN - 1) // _ALIGN * _ALIGN
     return out
+
+
+def group_ranges(specs, frozen, skipped, optim, lr, betas, eps):
+    """([(begin, count, skipped, decay, group)], hyper_table): optim_ranges() split further wherever the group index changes
+    (optim.group_of(name): the first optim.ParamGroup whose `match` hits the name, else 0, the default group). The decay
+    flag is optim.group_decays(name): an explicit group weight_decay reaches every tensor of the group. Neighbours merge, slot padding
+    included, while they share the count of sat-out steps, the flag AND the group. hyper_table is optim.hyper_table(lr, betas, eps):
+    one (lr, beta1, beta2, eps, weight_decay, amsgrad) per group, the call's own values in row 0. Pure: the host tests call it."""
+    out, slot_end = [], None
+    for s in sorted(specs, key=lambda s: s.offset):
+        if s.name in frozen:
+            slot_end = None
+            continue
+        k, d, q = int(skipped.get(s.name, 0)), bool(optim.group_decays(s.name)), int(optim.group_of(s.name))
+        if out and slot_end == s.offset and out[-1][2:] == (k, d, q):
+            out[-1] = (out[-1][0], s.offset + s.numel - out[-1][0], k, d, q)
+        else:
+            out.append((s.offset, s.numel, k, d, q))
+        slot_end = s.offset + (s.numel + _ALIGN - 1) // _ALIGN * _ALIGN
+    if len(out) > ops.ADAM_RANGES_MAX:
+        raise GoalnetError(f"{len(out)} trainable ranges (split by weight decay and parameter group): the fused step takes {ops.ADAM_RANGES_MAX}")
+    return out, optim.hyper_table(lr, betas, eps)
 
 
 class AVM(_LazyFlags, nn.Module):
@@ -363,6 +385,7 @@ class AVM(_LazyFlags, nn.Module):
 
         self._specs: List[_Spec] = []
         self._arena = self._garena = self._adam_m = self._adam_v = None
+        self._adam_vmax = None             # AMSGrad's running maximum of v: laid out like _adam_v, allocated by the first AMSGrad step
         self._hw3 = self._l2 = None
         self._adam_t = 0
         self._adam_segs = None
@@ -1877,8 +1900,14 @@ class AVM(_LazyFlags, nn.Module):
     def _optim_step(self, lr, betas, eps, grad_scale, optim, frozen, _tick, _guard, ema=None, grads=None):
         """adam_step under non-trivial options: the squared norm of the trainable gradients (clipping only; after the gradient exchange,
         so grad_scale carries 1 / world) and ONE launch over the trainable ranges, split where the decay flag changes. The learning
-        rate is the schedule's at the device step counter; 16-bit copy and fp16 guard pass through as in _adam_piece."""
-        ranges = optim_ranges(self._specs, frozen, self._sat_out, optim)
+        rate is the schedule's at the device step counter; 16-bit copy and fp16 guard pass through as in _adam_piece. With parameter
+        groups or AMSGrad the ranges are group_ranges() — split where the group changes too — and the one launch is
+        ops.group_step_dev_ranges over its table of hyper-parameters, with the vmax arena where a group runs under AMSGrad."""
+        grouped = bool(optim.groups or optim.amsgrad)     # DESIGN.md §4.17: the launch over a table of hyper-parameters
+        if grouped:
+            ranges, table = group_ranges(self._specs, frozen, self._sat_out, optim, lr, betas, eps)
+        else:
+            ranges = optim_ranges(self._specs, frozen, self._sat_out, optim)
         if len(ranges) > ops.ADAM_RANGES_MAX:
             raise GoalnetError(f"{len(ranges)} trainable ranges (split by weight decay): the fused step takes {ops.ADAM_RANGES_MAX}")
         segs = self._adam_state()
@@ -1887,7 +1916,12 @@ class AVM(_LazyFlags, nn.Module):
         s5 = self.spec("visbl.linear5.weight")
         shadow = self._w5b if (s5.name not in frozen and self._w5b is not None and self._w5b_version == self._w5_version()) else None
         g = self._garena if grads is None else grads
-        if ranges:
+        if ranges and grouped:
+            sumsq = ops.grad_sumsq(g, [r[:4] for r in ranges]) if optim.max_grad_norm is not None else None
+            vmax = self._ensure_vmax() if any(table[r[4]][5] for r in ranges) else None
+            ops.group_step_dev_ranges(self._arena, g, self._adam_m, self._adam_v, vmax, ranges, table, optim, self._state[0], grad_scale,
+                                      sumsq=sumsq, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
+        elif ranges:
             sumsq = ops.grad_sumsq(g, ranges) if optim.max_grad_norm is not None else None
             ops.optim_step_dev_ranges(self._arena, g, self._adam_m, self._adam_v, ranges, lr, betas[0], betas[1], eps, optim,
                                       self._state[0], grad_scale, sumsq=sumsq, shadow=shadow, shadow_begin=s5.offset, bad_step=_guard)
@@ -1896,6 +1930,25 @@ class AVM(_LazyFlags, nn.Module):
             self._ema_update(ema, frozen, _guard)
         if _tick:
             ops.counter_add(self._state[0], 1)
+
+    # ------------------------------------------------------------------------------------------
+    # AMSGrad's fourth state arena
+    # ------------------------------------------------------------------------------------------
+    def _ensure_vmax(self):
+        """the running maximum of v: whole-arena and zero-filled like _adam_v, allocated by the first AMSGrad step and kept in place
+        thereafter — captured graphs hold its address"""
+        if self._adam_vmax is None:
+            self._adam_vmax = torch.zeros_like(self._adam_v)
+        return self._adam_vmax
+
+    def vmax_of(self, name) -> torch.Tensor:
+        """AMSGrad's running maximum of exp_avg_sq (torch's max_exp_avg_sq) of a parameter as a view with the reference's logical
+        shape, like ema_of; zero for tensors that never ran under AMSGrad."""
+        if self._adam_vmax is None:
+            raise GoalnetError("no AMSGrad state yet: step with optim.OptimOptions(amsgrad=True) or a ParamGroup(amsgrad=True) first")
+        s = self.spec(name)
+        v = self._view(self._adam_vmax, s)
+        return v.reshape(s.shape[0], -1) if s.kind == "lin5" else v
 
     # ------------------------------------------------------------------------------------------
     # the weight average (DESIGN.md §4.15)
@@ -1975,7 +2028,7 @@ class AVM(_LazyFlags, nn.Module):
     def training_state(self) -> dict:
         """Everything a run needs to continue as if it had not stopped, as CPU tensors and plain Python values (`torch.save` takes
         it): "model" = state_dict() — the reference's keys and layouts, so the file doubles as a reference checkpoint —, the Adam
-        moments and the weight average as flat arenas in the arena's own layout, the four device counters and the two fp16 guard
+        moments (with AMSGrad's "adam_vmax", None before its first step) and the weight average as flat arenas in the arena's own layout, the four device counters and the two fp16 guard
         words, the host mirrors of the step and dropout counts, dropout seed and mode, the per-tensor counts of sat-out steps and the
         frozen set the fp16 path pinned, the loss-scale fields, and what identifies the model (load_training_state checks it). One
         host synchronisation."""
@@ -1994,7 +2047,7 @@ class AVM(_LazyFlags, nn.Module):
             **self._identity(),
             "model": self.state_dict(),
             "arena_numel": int(self._arena_numel),
-            "adam_m": cpu(self._adam_m), "adam_v": cpu(self._adam_v), "ema": cpu(self._ema),
+            "adam_m": cpu(self._adam_m), "adam_v": cpu(self._adam_v), "adam_vmax": cpu(self._adam_vmax), "ema": cpu(self._ema),
             "counters": cpu(self._state), "guard": cpu(self._guard),
             "adam_t": int(self._adam_t), "drop_step": int(self._drop_step),
             "dropout_seed": int(self.dropout_seed), "dropout_mode": self.dropout_mode,
@@ -2035,6 +2088,13 @@ class AVM(_LazyFlags, nn.Module):
         elif self._adam_m is not None:
             self._adam_m.zero_()
             self._adam_v.zero_()
+        vmax = state.get("adam_vmax")                                   # a state from before AMSGrad has no such key: no AMSGrad state yet
+        if vmax is not None:
+            if self._adam_m is None or vmax.numel() != self._adam_v.numel():
+                raise RuntimeError("load_training_state: AMSGrad's arena does not match the moments'")
+            self._ensure_vmax().copy_(vmax)
+        elif self._adam_vmax is not None:
+            self._adam_vmax.zero_()
         if state["ema"] is not None:
             self._ensure_ema().copy_(state["ema"])
         if self._state is None:
@@ -2068,14 +2128,19 @@ class AVM(_LazyFlags, nn.Module):
         norm = ops.grad_sumsq(self._gacc if self._norm_of_acc else self._garena, ranges).sqrt_()
         return norm / self._arena_grad_scale if self._arena_grad_scale != 1.0 else norm
 
-    def current_lr(self, lr=1e-3, optim=None) -> float:
+    def current_lr(self, lr=1e-3, optim=None, group=None) -> float:
         """the learning rate the next optimizer step runs at under `optim` (optim.OptimOptions; None: `lr`), evaluated by the device from
-        its step counter (ops.optim_lr). One read-back."""
+        its step counter (ops.optim_lr). `group`: the rate of that row of optim.hyper_table() — 0 the default group, i + 1
+        optim.groups[i] (ops.group_lr). One read-back."""
+        if group is not None and (optim is None or isinstance(group, bool) or not isinstance(group, int) or not 0 <= group <= len(optim.groups)):
+            raise ValueError(f"group must be an index into the default group and optim.groups, got {group!r}")
         if optim is None:
             return float(lr)
         self._require_device()
         if self._state is None:
             self._make_state()
+        if group is not None:
+            return float(ops.group_lr(optim.hyper_table(lr, (0.9, 0.999), 1e-8), group, optim, self._state[0]).item())
         return float(ops.optim_lr(lr, optim, self._state[0]).item())
 
     def make_optimizer(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):

@@ -19,6 +19,17 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
     p = p - step_size * (m / denom);           // param.addcdiv_(exp_avg, denom, value = -step_size)
 }
 
+// AMSGrad: torch's _single_tensor_adam(amsgrad=True). m and v as in adam1; the denominator comes from the running maximum of v.
+__device__ __forceinline__ void adam1_amsgrad(float& p, float g, float& m, float& v, float& vmax, float b2, float omb1, float omb2,
+                                              float eps, float step_size, float bc2_sqrt, float gs) {
+    g *= gs;
+    m = m + omb1 * (g - m);
+    v = v * b2 + (omb2 * g) * g;
+    vmax = (vmax >= v || vmax != vmax) ? vmax : v;   // torch.maximum(max_exp_avg_sq, exp_avg_sq): a NaN on either side stays (not fmaxf)
+    const float denom = sqrtf(vmax) / bc2_sqrt + eps;
+    p = p - step_size * (m / denom);
+}
+
 // The scalars torch's _single_tensor_adam computes as python floats (doubles), computed in fp64 for the 1-based step count ti.
 struct AdamScalars { float step_size, bc2_sqrt, b2, omb1, omb2; };
 

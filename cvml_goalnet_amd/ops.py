@@ -1075,6 +1075,58 @@ def optim_lr(lr, optim, step, out=None):
     return out
 
 
+# ---- parameter groups and AMSGrad on the fused step (include/goalnet_groups.h, DESIGN.md §4.17) ----
+GROUPS_MAX = _lib.GROUPS_MAX               # rows of one launch's hyper-parameter table, the default group included
+
+
+def _group_table(who, table):
+    """[(lr, beta1, beta2, eps, weight_decay, amsgrad)] -> goalnet_group_hyper[]"""
+    _req(1 <= len(table) <= GROUPS_MAX, f"{who}: 1..{GROUPS_MAX} groups")
+    return (_lib.GroupHyper * len(table))(*[_lib.GroupHyper(float(lr), float(b1), float(b2), float(eps), float(wd), int(bool(ams)), 0)
+                                            for lr, b1, b2, eps, wd, ams in table])
+
+
+def group_step_dev_ranges(p, g, m, v, vmax, ranges, table, optim, step, grad_scale=1.0, sumsq=None, shadow=None, shadow_begin=0,
+                          bad_step=None):
+    """optim_step_dev_ranges over `ranges` = [(begin, count, skipped, decay, group)] in ONE launch, every range under its row of `table` =
+    [(lr, beta1, beta2, eps, weight_decay, amsgrad)] (optim.OptimOptions.hyper_table): schedule, clipping and `decoupled` come from
+    `optim`, rate, betas, eps, decay value and AMSGrad from the row. `vmax`: the running maximum of v, required iff a referenced row
+    has amsgrad. A row with the single-rate call's values and no AMSGrad gives optim_step_dev_ranges' bits."""
+    _chk(p, g, m, v, vmax, shadow, sumsq)
+    n = p.numel()
+    _req(g.numel() == n and m.numel() == n and v.numel() == n, "group_step_dev_ranges: p, g, m, v must have the same size")
+    _req(vmax is None or (vmax.dtype == F32 and vmax.is_contiguous() and vmax.numel() == n),
+         "group_step_dev_ranges: vmax must be a contiguous fp32 arena of the size of v")
+    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"group_step_dev_ranges: 1..{_lib.ADAM_RANGES_MAX} ranges")
+    _req(all(b >= 0 and c > 0 and b + c <= n for b, c, _, _, _ in ranges), "group_step_dev_ranges: a range leaves the arena")
+    arr = (_lib.GroupRange * len(ranges))(*[_lib.GroupRange(int(b), int(c), int(k), int(bool(d)), int(q)) for b, c, k, d, q in ranges])
+    tab = _group_table("group_step_dev_ranges", table)
+    _req((sumsq is None) == (optim.max_grad_norm is None), "group_step_dev_ranges: sumsq goes with max_grad_norm, and only with it")
+    _req(sumsq is None or (sumsq.dtype == torch.float64 and sumsq.numel() == 1), "group_step_dev_ranges: sumsq must be one float64")
+    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
+         "group_step_dev_ranges: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
+    opts = _optim_opts(table[0][0], table[0][1], table[0][2], table[0][3], optim)
+    check(lib().goalnet_group_step_dev_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), arr, len(ranges), tab,
+                                              len(table), ctypes.byref(opts), _ctr(step), grad_scale, _p(sumsq), _p(shadow),
+                                              int(shadow_begin), 0 if shadow is None else shadow.numel(),
+                                              0 if shadow is None else _f16(shadow), 0 if bad_step is None else _ctr(bad_step), _s()),
+          "group_step_dev_ranges")
+
+
+def group_lr(table, group, optim, step, out=None):
+    """the learning rate of row `group` of `table` for the step that starts from *step completed steps, as the device evaluates it,
+    into out (1,) float64"""
+    _chk(out)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=step.device)
+    _req(out.dtype == torch.float64 and out.numel() == 1, "group_lr: out must be one float64")
+    tab = _group_table("group_lr", table)
+    _req(0 <= int(group) < len(table), "group_lr: no such group")
+    opts = _optim_opts(table[0][0], table[0][1], table[0][2], table[0][3], optim)
+    check(lib().goalnet_group_lr(ctypes.byref(opts), tab, int(group), _ctr(step), out.data_ptr(), _s()), "group_lr")
+    return out
+
+
 # ---- the weight average behind the fused step (include/goalnet_ema.h, DESIGN.md §4.15) ----
 def _plain_ranges(who, ranges, n):
     """[(begin, count)] or [(begin, count, skipped)] -> goalnet_adam_range[] (the count of sat-out steps is not read)"""

@@ -14,7 +14,13 @@ backward. State (`exp_avg`, `exp_avg_sq`, step) lives in the model (`AVM._adam_m
 EXTENSION: `OptimOptions` — weight decay (coupled as `torch.optim.Adam(weight_decay=)`, decoupled as
 `torch.optim.AdamW`), clipping by the global gradient norm (`torch.nn.utils.clip_grad_norm_`) and a learning-rate schedule that the
 device evaluates from its step counter — for `AVM.train_step(optim=)`, `AVM.adam_step(optim=)`, `loop.VideoTrainer(optim=)` and the
-drop-in `Adam(weight_decay=, max_grad_norm=, options=)` / `AdamW`. No AMSGrad, no per-tensor rates.
+drop-in `Adam(weight_decay=, max_grad_norm=, options=)` / `AdamW`.
+
+EXTENSION: parameter groups and AMSGrad — `OptimOptions(groups=(ParamGroup(("visbl.",), lr=1e-4), ...), amsgrad=)`
+gives the tensors whose names match their own rate, betas, eps, weight decay and AMSGrad flag, still in ONE launch over the arena
+(`goalnet_group_step_dev_ranges`, csrc/groups.hip); the running maximum of `exp_avg_sq` lives in a fourth arena (`AVM.vmax_of`). The
+drop-in `Adam` / `AdamW` take `amsgrad=` and torch's list of parameter-group dicts, and read each group's current `lr` at every
+`step()`, so stock `torch.optim.lr_scheduler`s drive them.
 
 EXTENSION: `EmaOptions` — an exponential moving average of the weights in a third arena, one launch behind every
 optimizer step, for the same four places (`ema=`); read it with `AVM.ema_of(name)` or evaluate / save under `with model.averaged():`.
@@ -36,6 +42,50 @@ def _is_int(x):
     return isinstance(x, int) and not isinstance(x, bool)
 
 
+def _real(x):
+    return isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x)
+
+
+GROUPS_MAX = 7                 # ParamGroups next to the default group: GOALNET_GROUPS_MAX - 1
+
+
+@dataclasses.dataclass(frozen=True)
+class ParamGroup:
+    """Hyper-parameters of their own for the tensors whose names contain one of the substrings in `match`. None
+    means the step's own value: the `lr`, `betas`, `eps` of the call, `OptimOptions.amsgrad`, and for `weight_decay` the options'
+    value under their `no_decay` rule. An explicit `weight_decay` applies to every tensor of the group, `no_decay` notwithstanding
+    (torch's param_groups know no such rule). The schedule scales a group's `lr` as it scales the step's."""
+    match: Tuple[str, ...]
+    lr: Optional[float] = None
+    betas: Optional[Tuple[float, float]] = None
+    eps: Optional[float] = None
+    weight_decay: Optional[float] = None
+    amsgrad: Optional[bool] = None
+
+    def __post_init__(self):
+        if isinstance(self.match, str) or not self.match or not all(isinstance(s, str) and s for s in self.match):
+            raise ValueError("match is a non-empty tuple of non-empty name substrings")
+        object.__setattr__(self, "match", tuple(self.match))
+        for k in ("lr", "eps", "weight_decay"):
+            x = getattr(self, k)
+            if x is not None:
+                if not _real(x) or x < 0:
+                    raise ValueError(f"{k} must be None or a finite number >= 0, got {x!r}")
+                object.__setattr__(self, k, float(x))
+        if self.betas is not None:
+            b = tuple(self.betas) if isinstance(self.betas, (tuple, list)) else ()
+            if len(b) != 2 or not all(_real(x) and 0.0 <= x < 1.0 for x in b):
+                raise ValueError(f"betas must be None or two numbers in [0, 1), got {self.betas!r}")
+            object.__setattr__(self, "betas", (float(b[0]), float(b[1])))
+        if self.amsgrad is not None:
+            if not isinstance(self.amsgrad, (bool, int)):
+                raise ValueError(f"amsgrad must be None or a bool, got {self.amsgrad!r}")
+            object.__setattr__(self, "amsgrad", bool(self.amsgrad))
+
+    def signature(self) -> tuple:
+        return (self.match, self.lr, self.betas, self.eps, self.weight_decay, self.amsgrad)
+
+
 @dataclasses.dataclass(frozen=True)
 class OptimOptions:
     """What the fused step does beyond torch.optim.Adam's defaults. Everything off by default: `trivial`, and the step is then exactly
@@ -44,7 +94,9 @@ class OptimOptions:
       no_decay                  name substrings of the tensors that get no decay, e.g. ("bias", "bnorm")
       max_grad_norm             None, or the cap on the L2 norm of all trainable gradients (torch.nn.utils.clip_grad_norm_)
       schedule                  "constant" | "cosine" (total_steps, min_lr) | "step" (step_period, gamma), after `warmup_steps` of
-                                linear warm-up; lr_at() is the closed form, the device evaluates the same from its step counter"""
+                                linear warm-up; lr_at() is the closed form, the device evaluates the same from its step counter
+      groups                    up to 7 ParamGroups: a tensor belongs to the first whose `match` hits its name, else to the default group
+      amsgrad                   AMSGrad (torch.optim.Adam(amsgrad=True)) for every tensor and group that does not say otherwise"""
     weight_decay: float = 0.0
     decoupled: bool = False
     no_decay: Tuple[str, ...] = ()
@@ -55,10 +107,19 @@ class OptimOptions:
     min_lr: float = 0.0
     step_period: Optional[int] = None
     gamma: float = 0.1
+    groups: Tuple[ParamGroup, ...] = ()
+    amsgrad: bool = False
 
     def __post_init__(self):
-        def real(x):
-            return isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x)
+        real = _real
+        if isinstance(self.groups, ParamGroup) or not all(isinstance(g, ParamGroup) for g in self.groups):
+            raise ValueError("groups is a tuple of optim.ParamGroup")
+        object.__setattr__(self, "groups", tuple(self.groups))
+        if len(self.groups) > GROUPS_MAX:
+            raise ValueError(f"at most {GROUPS_MAX} groups next to the default group, got {len(self.groups)}")
+        if not isinstance(self.amsgrad, (bool, int)):
+            raise ValueError(f"amsgrad must be a bool, got {self.amsgrad!r}")
+        object.__setattr__(self, "amsgrad", bool(self.amsgrad))
         if not real(self.weight_decay) or self.weight_decay < 0:
             raise ValueError(f"weight_decay must be a finite number >= 0, got {self.weight_decay!r}")
         if isinstance(self.no_decay, str) or not all(isinstance(s, str) and s for s in self.no_decay):
@@ -89,14 +150,49 @@ class OptimOptions:
     @property
     def trivial(self) -> bool:
         """nothing is switched on: the step is the one without options, launch for launch"""
-        return self.weight_decay == 0 and self.max_grad_norm is None and self.schedule == "constant" and self.warmup_steps == 0
+        return (self.weight_decay == 0 and self.max_grad_norm is None and self.schedule == "constant" and self.warmup_steps == 0
+                and not self.grouped)
+
+    @property
+    def grouped(self) -> bool:
+        """groups or AMSGrad: the step is the launch over a table of hyper-parameters (ops.group_step_dev_ranges)"""
+        return bool(self.groups) or self.amsgrad
 
     def signature(self) -> tuple:
-        """hashable: everything a captured step bakes in about the options (() when trivial)"""
+        """hashable: everything a captured step bakes in about the options (() when trivial). Without groups and AMSGrad it is the
+        tuple it always was (saved trainer states compare it); otherwise the groups and the flag are appended."""
         if self.trivial:
             return ()
-        return (float(self.weight_decay), self.decoupled, self.no_decay, None if self.max_grad_norm is None else float(self.max_grad_norm),
-                self.schedule, self.warmup_steps, self.total_steps, float(self.min_lr), self.step_period, float(self.gamma))
+        sig = (float(self.weight_decay), self.decoupled, self.no_decay, None if self.max_grad_norm is None else float(self.max_grad_norm),
+               self.schedule, self.warmup_steps, self.total_steps, float(self.min_lr), self.step_period, float(self.gamma))
+        if self.grouped:
+            sig += (tuple(g.signature() for g in self.groups), self.amsgrad)
+        return sig
+
+    def group_of(self, name: str) -> int:
+        """the tensor's row in hyper_table(): 1 + the index of the first group whose `match` hits the name, 0 (the default group) else"""
+        for i, g in enumerate(self.groups):
+            if any(s in name for s in g.match):
+                return i + 1
+        return 0
+
+    def group_decays(self, name: str) -> bool:
+        """weight decay applies to the tensor of this name under its group: an explicit group value reaches every tensor of the group,
+        otherwise it is decays()"""
+        k = self.group_of(name)
+        if k and self.groups[k - 1].weight_decay is not None:
+            return self.groups[k - 1].weight_decay > 0
+        return self.decays(name)
+
+    def hyper_table(self, lr, betas, eps) -> list:
+        """[(lr, beta1, beta2, eps, weight_decay, amsgrad)]: row 0 the default group — the call's own values —, row i + 1 groups[i]
+        with every None filled in from row 0"""
+        rows = [(float(lr), float(betas[0]), float(betas[1]), float(eps), float(self.weight_decay), self.amsgrad)]
+        for g in self.groups:
+            b = rows[0][1:3] if g.betas is None else g.betas
+            rows.append((rows[0][0] if g.lr is None else g.lr, b[0], b[1], rows[0][3] if g.eps is None else g.eps,
+                         rows[0][4] if g.weight_decay is None else g.weight_decay, self.amsgrad if g.amsgrad is None else g.amsgrad))
+        return rows
 
     def decays(self, name: str) -> bool:
         """weight decay applies to the tensor of this name"""
@@ -180,17 +276,38 @@ def _options(options, weight_decay, max_grad_norm, decoupled):
     return OptimOptions(weight_decay=0.0 if weight_decay is None else weight_decay, decoupled=decoupled, max_grad_norm=max_grad_norm)
 
 
+GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "amsgrad")     # what a parameter-group dict of the drop-in optimizers may set
+
+
 class Adam(torch.optim.Optimizer):
     _decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None, weight_decay=None, max_grad_norm=None,
-                 options: Optional[OptimOptions] = None, ema: Optional[EmaOptions] = None):
+                 options: Optional[OptimOptions] = None, ema: Optional[EmaOptions] = None, amsgrad=False):
         params = list(params)
         if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameters")
+        if not isinstance(amsgrad, (bool, int)):
+            raise ValueError(f"amsgrad must be a bool, got {amsgrad!r}")
         self.options = _options(options, weight_decay, max_grad_norm, self._decoupled)       # ValueError before anything is launched
+        if self.options.groups:
+            raise ValueError("pass parameter groups as torch does, a list of dicts in place of the parameters, not inside options")
         self.ema = _ema(ema)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        self._grouped = bool(params) and isinstance(params[0], dict)
+        if self._grouped:
+            if len(params) > GROUPS_MAX:
+                raise ValueError(f"at most {GROUPS_MAX} parameter groups, got {len(params)}")
+            for i, g in enumerate(params):
+                extra = sorted(set(g) - {"params", *GROUP_KEYS})
+                if extra:
+                    raise ValueError(f"parameter group {i}: unknown key(s) {extra}; a group sets 'params' and any of {GROUP_KEYS}")
+                ParamGroup(("x",), **{k: g[k] for k in GROUP_KEYS if g.get(k) is not None})      # its validation, before anything runs
+        self._amsgrad = bool(amsgrad) or self.options.amsgrad
+        # weight_decay / amsgrad None in a group: the options' value (under their no_decay rule) / the constructor's flag
+        defaults = dict(lr=lr, betas=betas, eps=eps)
+        if self._grouped:
+            defaults.update(weight_decay=None, amsgrad=None)
+        super().__init__(params, defaults)
         self._model = model
 
     def _find_model(self):
@@ -208,17 +325,26 @@ class Adam(torch.optim.Optimizer):
         m = self._find_model()
         if m._garena is None:
             raise RuntimeError("step() before any backward: there are no gradients")
-        if len(self.param_groups) != 1:
-            raise RuntimeError("one parameter group: the arena is updated in one pass")
-        g = self.param_groups[0]
         # as torch.optim.Adam skips a parameter whose grad is None, the pass skips the tensors that were frozen (requires_grad=False)
         # in the last backward: the optimizer holds either all parameters or exactly the trainable ones
-        every = {id(getattr(*m._module_of(s.name))) for s in m._specs}
-        trainable = {id(getattr(*m._module_of(s.name))) for s in m._specs if s.name not in m._bwd_frozen}
-        if {id(p) for p in g["params"]} not in (every, trainable):
+        name_of = {id(getattr(*m._module_of(s.name))): s.name for s in m._specs}
+        every = set(name_of)
+        trainable = {i for i, n in name_of.items() if n not in m._bwd_frozen}
+        held = [id(p) for g in self.param_groups for p in g["params"]]
+        if set(held) not in (every, trainable) or len(held) != len(set(held)):
             raise RuntimeError("cvml_goalnet_amd.optim.Adam steps ALL parameters of its AVM (model.parameters()), or all that have "
                                "requires_grad=True (filter(lambda p: p.requires_grad, model.parameters()))")
-        m.adam_step(g["lr"], tuple(g["betas"]), g["eps"], optim=None if self.options.trivial else self.options, ema=self.ema)
+        g = self.param_groups[0]
+        if len(self.param_groups) == 1 and not self._amsgrad and not g.get("amsgrad") and g.get("weight_decay") is None:
+            m.adam_step(g["lr"], tuple(g["betas"]), g["eps"], optim=None if self.options.trivial else self.options, ema=self.ema)
+            return loss
+        # one ParamGroup per torch group, matched by the full tensor names and read NOW: a stock lr_scheduler has moved the rates
+        groups = ()
+        if self._grouped:
+            groups = tuple(ParamGroup(tuple(name_of[id(p)] for p in grp["params"]), lr=grp["lr"], betas=tuple(grp["betas"]), eps=grp["eps"],
+                                      weight_decay=grp.get("weight_decay"), amsgrad=grp.get("amsgrad")) for grp in self.param_groups)
+        opt = dataclasses.replace(self.options, groups=groups, amsgrad=self._amsgrad)
+        m.adam_step(g["lr"], tuple(g["betas"]), g["eps"], optim=opt, ema=self.ema)
         return loss
 
     def zero_grad(self, set_to_none: bool = True):
@@ -233,8 +359,8 @@ class AdamW(Adam):
     _decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, model: AVM = None, weight_decay=None, max_grad_norm=None,
-                 options: Optional[OptimOptions] = None, ema: Optional[EmaOptions] = None):
+                 options: Optional[OptimOptions] = None, ema: Optional[EmaOptions] = None, amsgrad=False):
         if options is None and weight_decay is None:
             weight_decay = 1e-2                     # torch.optim.AdamW's default
         super().__init__(params, lr=lr, betas=betas, eps=eps, model=model, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                         options=options, ema=ema)
+                         options=options, ema=ema, amsgrad=amsgrad)

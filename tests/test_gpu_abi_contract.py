@@ -34,61 +34,13 @@ from _abi_shapes import (BF16_CONV, BF16_LINEAR_BWD, BF16_LINEAR_FWD, BF16_WGRAD
                          CONV_WGRAD, LINEAR_DW, LINEAR_DX, LINEAR_FWD, MLP_ROWS, O16_CONV, O16_LINEAR, POOL, SPLIT_CONV, SPLIT_LINEAR)
 
 
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ok(rc, what):
-    _lib.check(rc, what)
-
-
-def _ws(bands, nbytes):
-    """a guarded workspace of exactly nbytes bytes (None when the entry point asks for none)"""
-    return bands.guarded(nbytes, torch.uint8, name="ws") if nbytes else None
-
-
-def _tiles128(rows, cols):
-    """the header: one ticket counter per 128 x 128 output tile"""
-    return ((rows + 127) // 128) * ((cols + 127) // 128)
-
-
-def _counters_clean(ctr, what):
-    assert not ctr.any().item(), f"{what}: {int((ctr != 0).sum())} ticket counters left non-zero"
+from _abi_cases import (_conv_fwd_call, _conv_fwd_case, _conv_wgrad_call, _conv_wgrad_case, _counters_clean, _linear_fwd_call,  # noqa: E402
+                        _linear_fwd_case, _ok, _s, _tiles128, _ws)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # conv3x3_fwd
 # ---------------------------------------------------------------------------------------------------------------------------
-def _conv_fwd_case(n, h, w, cin, cout, affine, bias, relu):
-    x = rnd(n, h, w, cin, seed=7)
-    sc = rnd(cin, seed=8, lo=0.5, hi=1.5) if affine else None
-    sh = rnd(cin, seed=9, lo=-0.5, hi=0.5) if affine else None
-    wt = rnd(cout, 3, 3, cin, seed=10, lo=-0.05, hi=0.05)
-    b = rnd(cout, seed=11) if bias else None
-    xn = x.double() * sc.double() + sh.double() if affine else x.double()
-    ref = F.conv2d(nchw(xn), wt.double().permute(0, 3, 1, 2), None if b is None else b.double(), padding=1)
-    return x, sc, sh, wt, b, nhwc(F.relu(ref) if relu else ref)
-
-
-def _conv_fwd_call(lib, bands, case, dims, relu, mode):
-    """mode: 'null' (ws = NULL: no split), 'ws' (split-K slabs + reduce launch), 'ctr' (slabs + ticket counters: fused reduce)"""
-    n, h, w, cin, cout = dims
-    x, sc, sh, wt, b, _ = case
-    xg, wg = bands.place(x, "x"), bands.place(wt, "w")
-    scg, shg, bg = (None if t is None else bands.place(t, nm) for t, nm in ((sc, "scale"), (sh, "shift"), (b, "bias")))
-    y = bands.guarded((n, h, w, cout), F32, name="y")
-    nbytes = lib.goalnet_conv3x3_fwd_ws_bytes(*dims) if mode != "null" else 0
-    ws = _ws(bands, nbytes)
-    nctr = _tiles128(n * h * w, cout)
-    ctr = bands.guarded(nctr, torch.int32, fill=0, name="tile_ctr") if mode == "ctr" else None
-
-    def call():
-        _ok(lib.goalnet_conv3x3_fwd(ptr(xg), ptr(scg), ptr(shg), ptr(wg), ptr(bg), int(relu), ptr(y), n, h, w, cin, cout, ptr(ws), nbytes,
-                                    ptr(ctr), nctr if ctr is not None else 0, _s()), "conv3x3_fwd")
-    call()
-    return y, ctr, call
-
-
 @pytest.mark.parametrize("n,h,w,cin,cout,affine,bias,relu", CONV_FWD)
 def test_conv3x3_fwd_guarded(n, h, w, cin, cout, affine, bias, relu):
     lib = _lib.load()
@@ -143,31 +95,12 @@ def test_conv3x3_wgrad_guarded(n, h, w, cin, cout, affine, path, monkeypatch):
     bits of the two-launch form; elsewhere the counters are not used, so the results are the same launches: identical either way."""
     monkeypatch.setenv("GOALNET_WGRAD_PATH", path)
     lib = _lib.load()
-    x = rnd(n, h, w, cin, seed=12)
-    sc = rnd(cin, seed=13, lo=0.5, hi=1.5) if affine else None
-    sh = rnd(cin, seed=14, lo=-0.5, hi=0.5) if affine else None
-    dy = rnd(n, h, w, cout, seed=15)
-    xn = x.double() * sc.double() + sh.double() if affine else x.double()
-    ref = torch.nn.grad.conv2d_weight(nchw(xn), (cout, cin, 3, 3), nchw(dy.double()), padding=1).permute(0, 2, 3, 1)
-    nbytes = lib.goalnet_conv3x3_wgrad_ws_bytes(n, h, w, cin, cout)
+    case = _conv_wgrad_case(n, h, w, cin, cout, affine)
+    ref = case[4]
     got = {}
     for mode in ("ws", "ctr", "nocodes"):
         bands = Bands()
-        xg, dyg = bands.place(x, "x"), bands.place(dy, "dy")
-        scg, shg = (None if t is None else bands.place(t, nm) for t, nm in ((sc, "scale"), (sh, "shift")))
-        dw = bands.guarded((cout, 3, 3, cin), F32, name="dw")
-        ws = _ws(bands, nbytes)
-        codes = None
-        if mode != "nocodes":
-            codes = bands.guarded(lib.goalnet_conv3x3_wgrad_codes_bytes(n, h, w), torch.uint8, name="codes")
-            _ok(lib.goalnet_conv3x3_wgrad_codes(ptr(codes), n, h, w, _s()), "conv3x3_wgrad_codes")
-        nctr = _tiles128(cout, 9 * cin)
-        ctr = bands.guarded(nctr, torch.int32, fill=0, name="tile_ctr") if mode == "ctr" else None
-
-        def call():
-            _ok(lib.goalnet_conv3x3_wgrad(ptr(xg), ptr(scg), ptr(shg), ptr(dyg), ptr(dw), ptr(ws), nbytes, ptr(codes), ptr(ctr),
-                                          nctr if ctr is not None else 0, n, h, w, cin, cout, _s()), "conv3x3_wgrad")
-        call()
+        dw, ctr, call = _conv_wgrad_call(lib, bands, case, (n, h, w, cin, cout), mode)
         close(f"conv3x3_wgrad[{n}x{h}x{w}x{cin}->{cout}] {path} {mode}", dw, ref, rtol=5e-6)
         bands.assert_bands_intact()
         got[mode] = dw.clone()
@@ -188,28 +121,10 @@ def test_conv3x3_wgrad_guarded(n, h, w, cin, cout, affine, path, monkeypatch):
 @pytest.mark.parametrize("m,k,j,affine,mask,ldextra", LINEAR_FWD)
 def test_linear_fwd_guarded(m, k, j, affine, mask, ldextra):
     lib = _lib.load()
-    x = rnd(m, k, seed=22)
-    w = rnd(j, k, seed=23, lo=-0.05, hi=0.05)
-    b = rnd(j, seed=24)
-    sc = rnd(512, seed=25, lo=0.5, hi=1.5) if affine else None
-    sh = rnd(512, seed=26, lo=-0.5, hi=0.5) if affine else None
-    dm = (torch.rand(m, j, generator=torch.Generator().manual_seed(27)) >= 0.2).float() * 1.25 if mask else None
-    xd = x.double()
-    if affine:
-        ch = torch.arange(k) % 512
-        xd = xd * sc.double()[ch] + sh.double()[ch]
-    pre = xd @ w.double().t() + b.double()
-    ref = F.relu(pre) * (dm.double() if mask else 1.0)
+    case = _linear_fwd_case(m, k, j, affine, mask)
+    dm, pre, ref = case[5:]
     bands = Bands()
-    xg, wg, bg = bands.place(x, "x"), bands.place(w, "w"), bands.place(b, "bias")
-    scg, shg, dmg = (None if t is None else bands.place(t, nm) for t, nm in ((sc, "scale"), (sh, "shift"), (dm, "dropmask")))
-    ld = j + ldextra
-    y = bands.guarded_rows(m, j, ld, F32, name="y")                # the gaps between the rows are bands too
-    mult = bands.guarded_rows(m, j, ld, F32, name="mult_out")
-    nbytes = lib.goalnet_linear_fwd_ws_bytes(m, k, j)
-    ws = _ws(bands, nbytes)
-    _ok(lib.goalnet_linear_fwd(ptr(xg), k, ptr(scg), ptr(shg), 512 if affine else 0, ptr(wg), ptr(bg), 1, ptr(dmg), j, ptr(y), ld,
-                               ptr(mult), ld, m, k, j, ptr(ws), nbytes, _s()), "linear_fwd")
+    y, mult, _ = _linear_fwd_call(lib, bands, case, (m, k, j), ldextra)
     close(f"linear_fwd[{m}x{k}->{j}]", y, ref, rtol=3e-6)
     want_mult = (pre > 0).double() * (dm.double() if mask else 1.0)
     safe = pre.abs() > 1e-4

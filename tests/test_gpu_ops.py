@@ -118,8 +118,8 @@ def test_conv1_fwd_and_wgrad(n, h, w, monkeypatch):
     (2, 11, 11, 256, 512, True, True, True),    # reference conv3 geometry
     (2, 11, 11, 512, 256, False, False, False), # data-gradient form of conv3
     (2, 13, 13, 256, 64, False, False, False),  # data-gradient form of conv2 (N tile mostly empty)
-    (16, 11, 11, 512, 256, False, False, False),# M = 1936: 16 M-tiles, ragged last tile
-    (16, 11, 11, 256, 512, True, True, True),
+    (16, 11, 11, 512, 256, False, False, False),# M = 1936: 16 M-tiles, ragged last tile; 32 tiles x 16 splits
+    (16, 11, 11, 256, 512, True, True, True),   # 64 tiles x 8 splits: the most tiles of the plain XCD-local order (tests/_split_classes.py)
     (1, 3, 3, 64, 128, True, False, True),
     (40, 26, 22, 256, 64, False, False, False), # 128 x 64 tile at M = 22 880 pixels (179 M-tiles, ragged last one), no split-K
     (3, 9, 7, 64, 32, True, True, True),        # 128 x 64 tile: 32 of its 64 columns valid, BatchNorm on the load, bias + ReLU
@@ -147,9 +147,9 @@ def test_conv3x3_fwd(n, h, w, cin, cout, affine, bias, relu):
     (3, 13, 13, 64, 256, True),
     (2, 11, 11, 256, 512, True),
     (5, 9, 6, 64, 128, False),
-    (16, 11, 11, 256, 512, True),     # M = 1936 -> 3 splits over the reduction
-    (16, 13, 13, 64, 256, True),      # M = 2704 -> 5 splits, 576 columns (4.5 N-tiles)
-    (40, 13, 13, 64, 256, False),
+    (16, 11, 11, 256, 512, True),     # M = 1936 -> 8 splits over the reduction, 72 tiles: the two-phase XCD-local order, one group
+    (16, 13, 13, 64, 256, True),      # M = 2704 -> 15 splits (two groups, padded grid), 576 columns (4.5 N-tiles)
+    (40, 13, 13, 64, 256, False),     # 43 splits, summed by the wide reduce kernel
     (2, 1, 9, 64, 128, True),         # one image row: first and last row coincide (every kh != 1 tap is padding)
     (3, 4, 1, 64, 128, True),         # one image column
     (1, 1, 1, 64, 128, True),

@@ -1,5 +1,5 @@
 // Adam (torch.optim.Adam defaults, single-tensor operation order): the per-element update and the scalars it runs under.
-// Shared by the arena passes (small.hip: adam_kernel, adam_ranges_kernel) and the GEMM epilogue that applies the update to
+// Shared by the arena passes (optim_impl.h's range_pass, behind adam.hip, optim.hip and groups.hip) and the GEMM epilogue that applies the update to
 // linear5.weight straight from the weight gradient's accumulators (gemm_f32.hip: gemm_f32_epi_kernel), so that every site
 // compiles the same expressions and produces the same bits.
 #pragma once

@@ -1,21 +1,16 @@
 // An exponential moving average of the weights behind the fused step, and the exchange of two arenas (include/goalnet_ema.h,
 // DESIGN.md §4.15). One pass over the trainable ranges, 12 bytes per parameter: read p, read and write e. Whether the pass copies,
 // averages or leaves e alone, and the weight it averages with, come from the device step counter — evaluated by every thread where
-// adam_scalars / sched_lr evaluate theirs — so a captured graph follows the count. Block-to-range mapping and tail are
-// adam_ranges_kernel's (small.hip).
+// adam_scalars / sched_lr evaluate theirs — so a captured graph follows the count. Block-to-range mapping, tail and the
+// host's range checks are ranges.h's.
 #include <math.h>
 
 #include "../../include/goalnet_ema.h"
-#include "common.h"
+#include "ranges.h"
 
 using namespace goalnet;
 
 namespace {
-
-struct EmaRanges {
-    int64_t begin[GOALNET_ADAM_RANGES_MAX], count[GOALNET_ADAM_RANGES_MAX];
-    int first_block[GOALNET_ADAM_RANGES_MAX + 1];
-};
 
 enum { EMA_SKIP = 0, EMA_COPY = 1, EMA_AVERAGE = 2 };
 
@@ -36,7 +31,7 @@ __device__ __forceinline__ int ema_plan(const goalnet_ema_opts& o, int64_t t, fl
 
 __device__ __forceinline__ float ema1(float e, float p, float w) { return fmaf(w, p - e, e); }
 
-__global__ __launch_bounds__(256) void ema_ranges_kernel(const float* __restrict__ p, float* __restrict__ e, EmaRanges rs, int nranges,
+__global__ __launch_bounds__(256) void ema_ranges_kernel(const float* __restrict__ p, float* __restrict__ e, RangeMap rs, int nranges,
                                                         goalnet_ema_opts o, const int64_t* __restrict__ step_dev, int64_t step_bias,
                                                         const int64_t* __restrict__ bad_step) {
     const int64_t t = *step_dev + step_bias;              // the step that has just been applied: what goalnet_grad_finite_check stamps
@@ -44,77 +39,40 @@ __global__ __launch_bounds__(256) void ema_ranges_kernel(const float* __restrict
     float w = 1.0f;
     const int plan = ema_plan(o, t, &w);
     if (plan == EMA_SKIP) return;
-    int r = 0;
-    while (r + 1 < nranges && (int)blockIdx.x >= rs.first_block[r + 1]) ++r;
-    const int64_t lb = (int)blockIdx.x - rs.first_block[r], nb = rs.first_block[r + 1] - rs.first_block[r];
-    const int64_t begin = rs.begin[r], n = rs.count[r], b4 = begin >> 2, n4 = n >> 2;
+    const BlockShare b = block_share(rs, nranges);
     if (plan == EMA_COPY) {
-        for (int64_t j = lb * blockDim.x + threadIdx.x; j < n4; j += nb * blockDim.x)
-            reinterpret_cast<uint4*>(e)[b4 + j] = reinterpret_cast<const uint4*>(p)[b4 + j];
-        if (lb == 0 && threadIdx.x < (n & 3)) {
-            const int64_t i = begin + (n4 << 2) + threadIdx.x;
-            reinterpret_cast<uint32_t*>(e)[i] = reinterpret_cast<const uint32_t*>(p)[i];
-        }
+        for_share(
+            b, [&](int64_t i) { reinterpret_cast<uint4*>(e)[i] = reinterpret_cast<const uint4*>(p)[i]; },
+            [&](int64_t i) { reinterpret_cast<uint32_t*>(e)[i] = reinterpret_cast<const uint32_t*>(p)[i]; });
         return;
     }
-    for (int64_t j = lb * blockDim.x + threadIdx.x; j < n4; j += nb * blockDim.x) {
-        const int64_t i = b4 + j;                         // float4 index in the arena
-        const float4 pp = reinterpret_cast<const float4*>(p)[i];
-        float4 ee = reinterpret_cast<float4*>(e)[i];
-        ee.x = ema1(ee.x, pp.x, w);
-        ee.y = ema1(ee.y, pp.y, w);
-        ee.z = ema1(ee.z, pp.z, w);
-        ee.w = ema1(ee.w, pp.w, w);
-        reinterpret_cast<float4*>(e)[i] = ee;
-    }
-    if (lb == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = begin + (n4 << 2) + threadIdx.x;
-        e[i] = ema1(e[i], p[i], w);
-    }
+    for_share(
+        b,
+        [&](int64_t i) {
+            const float4 pp = reinterpret_cast<const float4*>(p)[i];
+            float4 ee = reinterpret_cast<float4*>(e)[i];
+            ee.x = ema1(ee.x, pp.x, w);
+            ee.y = ema1(ee.y, pp.y, w);
+            ee.z = ema1(ee.z, pp.z, w);
+            ee.w = ema1(ee.w, pp.w, w);
+            reinterpret_cast<float4*>(e)[i] = ee;
+        },
+        [&](int64_t i) { e[i] = ema1(e[i], p[i], w); });
 }
 
-__global__ __launch_bounds__(256) void swap_ranges_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, EmaRanges rs, int nranges) {
-    int r = 0;
-    while (r + 1 < nranges && (int)blockIdx.x >= rs.first_block[r + 1]) ++r;
-    const int64_t lb = (int)blockIdx.x - rs.first_block[r], nb = rs.first_block[r + 1] - rs.first_block[r];
-    const int64_t begin = rs.begin[r], n = rs.count[r], b4 = begin >> 2, n4 = n >> 2;
-    for (int64_t j = lb * blockDim.x + threadIdx.x; j < n4; j += nb * blockDim.x) {
-        const int64_t i = b4 + j;
-        const uint4 x = reinterpret_cast<uint4*>(a)[i], y = reinterpret_cast<uint4*>(b)[i];
-        reinterpret_cast<uint4*>(a)[i] = y;
-        reinterpret_cast<uint4*>(b)[i] = x;
-    }
-    if (lb == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = begin + (n4 << 2) + threadIdx.x;
-        const uint32_t x = a[i], y = b[i];
-        a[i] = y;
-        b[i] = x;
-    }
-}
-
-int blocks_for(int64_t n4) {
-    int64_t b = (n4 + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-int check_ranges(const char* who, const goalnet_adam_range* ranges, int count, EmaRanges* rs) {
-    GN_REQUIRE(ranges, GOALNET_E_NULL, "%s: null pointer", who);
-    GN_REQUIRE(count >= 1 && count <= GOALNET_ADAM_RANGES_MAX, GOALNET_E_SHAPE, "%s: 1..%d ranges", who, GOALNET_ADAM_RANGES_MAX);
-    int64_t end = 0;
-    rs->first_block[0] = 0;
-    for (int r = 0; r < count; ++r) {
-        const goalnet_adam_range& a = ranges[r];
-        GN_REQUIRE(a.begin >= 0 && a.count > 0, GOALNET_E_SHAPE, "%s: range %d is empty or starts below 0", who, r);
-        GN_REQUIRE((a.begin & 3) == 0, GOALNET_E_ALIGN, "%s: range %d must begin at a multiple of 4 elements", who, r);
-        GN_REQUIRE(a.begin >= end, GOALNET_E_SHAPE, "%s: range %d overlaps its predecessor or is out of order", who, r);
-        end = a.begin + a.count;
-        rs->begin[r] = a.begin;
-        rs->count[r] = a.count;
-        rs->first_block[r + 1] = rs->first_block[r] + blocks_for(a.count >> 2);
-    }
-    return 0;
+__global__ __launch_bounds__(256) void swap_ranges_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, RangeMap rs, int nranges) {
+    for_share(
+        block_share(rs, nranges),
+        [&](int64_t i) {
+            const uint4 x = reinterpret_cast<uint4*>(a)[i], y = reinterpret_cast<uint4*>(b)[i];
+            reinterpret_cast<uint4*>(a)[i] = y;
+            reinterpret_cast<uint4*>(b)[i] = x;
+        },
+        [&](int64_t i) {
+            const uint32_t x = a[i], y = b[i];
+            a[i] = y;
+            b[i] = x;
+        });
 }
 
 }  // namespace
@@ -124,8 +82,8 @@ extern "C" {
 int goalnet_ema_update_dev_ranges(const float* p, float* e, const goalnet_adam_range* ranges, int count, const goalnet_ema_opts* opts,
                                   const int64_t* step, int64_t step_bias, const int64_t* bad_step, void* stream) {
     GN_REQUIRE(p && e && step, GOALNET_E_NULL, "ema_update_dev_ranges: null pointer");
-    EmaRanges rs;
-    const int rc = check_ranges("ema_update_dev_ranges", ranges, count, &rs);
+    RangeMap rs;
+    const int rc = map_ranges("ema_update_dev_ranges", ranges, count, RANGE_BLOCKS_MAX, &rs);
     if (rc != 0) return rc;
     GN_REQUIRE(opts, GOALNET_E_NULL, "ema_update_dev_ranges: null options");
     GN_REQUIRE(isfinite(opts->decay) && opts->decay >= 0.0 && opts->decay < 1.0, GOALNET_E_VALUE, "ema_update_dev_ranges: decay must be in [0, 1)");
@@ -143,8 +101,8 @@ int goalnet_ema_update_dev_ranges(const float* p, float* e, const goalnet_adam_r
 
 int goalnet_swap_ranges(float* a, float* b, const goalnet_adam_range* ranges, int count, void* stream) {
     GN_REQUIRE(a && b, GOALNET_E_NULL, "swap_ranges: null pointer");
-    EmaRanges rs;
-    const int rc = check_ranges("swap_ranges", ranges, count, &rs);
+    RangeMap rs;
+    const int rc = map_ranges("swap_ranges", ranges, count, RANGE_BLOCKS_MAX, &rs);
     if (rc != 0) return rc;
     GN_REQUIRE(a != b, GOALNET_E_VALUE, "swap_ranges: the two arenas are the same");
     GN_REQUIRE(aligned16(a) && aligned16(b), GOALNET_E_ALIGN, "swap_ranges: arenas must be 16-byte aligned");

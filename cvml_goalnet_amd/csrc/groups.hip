@@ -1,7 +1,8 @@
 // Parameter groups and AMSGrad on the fused step (include/goalnet_groups.h): optim.hip's launch with a table of up
 // to GOALNET_GROUPS_MAX hyper-parameter sets, one index per range, and a fourth state arena for the running maximum of v. Schedule,
-// per-element expressions, block-to-range mapping, tail, 16-bit copy and guard are optim_impl.h's, which optim.hip compiles too: a
-// range whose group carries the single-rate call's hyper-parameters and no AMSGrad gives goalnet_optim_step_dev_ranges' bits.
+// per-element expressions, 16-bit copy and the block's whole pass (optim_block) are optim_impl.h's, which optim.hip compiles too;
+// block-to-range mapping and tail are ranges.h's. A range whose group carries the single-rate call's hyper-parameters and no AMSGrad
+// gives goalnet_optim_step_dev_ranges' bits.
 #include "../../include/goalnet_groups.h"
 #include "optim_impl.h"
 
@@ -9,54 +10,31 @@ using namespace goalnet;
 
 namespace {
 
-struct GroupRanges {
-    int64_t begin[GOALNET_ADAM_RANGES_MAX], count[GOALNET_ADAM_RANGES_MAX], skipped[GOALNET_ADAM_RANGES_MAX];
-    int first_block[GOALNET_ADAM_RANGES_MAX + 1];
-    uint32_t decay;                                      // bit r: weight decay applies to range r
-    uint8_t group[GOALNET_ADAM_RANGES_MAX];              // range r runs under groups.h[group[r]]
+struct GroupSteps {
+    int64_t skipped[GOALNET_ADAM_RANGES_MAX];
+    uint64_t decay;                                      // bit r: weight decay applies to range r
+    uint8_t group[GOALNET_ADAM_RANGES_MAX];              // range r runs under GroupTable::h[group[r]]
 };
 
 struct GroupTable { goalnet_group_hyper h[GOALNET_GROUPS_MAX]; };
 
-// HIP passes at most 4 KB of kernel arguments: the three structures by value, 10 pointers / 8-byte integers and 4 ints, with padding
-static_assert(sizeof(GroupRanges) + sizeof(GroupTable) + sizeof(goalnet_optim_opts) + 10 * 8 + 4 * 8 <= 4096,
+// HIP passes at most 4 KB of kernel arguments: the four structures by value (648 + 296 + 384 + 96 bytes), 10 pointers / 8-byte integers
+// and 4 ints, with padding
+static_assert(sizeof(RangeMap) + sizeof(GroupSteps) + sizeof(GroupTable) + sizeof(goalnet_optim_opts) + 10 * 8 + 4 * 8 <= 4096,
               "group_ranges_kernel's arguments must fit HIP's 4 KB");
 static_assert(sizeof(goalnet_group_hyper) == 48 && sizeof(goalnet_group_range) == 32, "the layouts include/goalnet_groups.h documents");
 
-__global__ void group_lr_kernel(goalnet_optim_opts o, const int64_t* __restrict__ step, double* __restrict__ lr_out) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *lr_out = sched_lr(o, *step);
-}
-
 __global__ __launch_bounds__(256) void group_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, float* __restrict__ vmax, GroupRanges rs, int nranges,
-                                                          GroupTable gt, goalnet_optim_opts o, const int64_t* __restrict__ step_dev, float gs,
-                                                          const double* __restrict__ sumsq, uint2* __restrict__ shadow, int64_t sh_b4,
+                                                          float* __restrict__ v, float* __restrict__ vmax, RangeMap rs, GroupSteps st,
+                                                          int nranges, GroupTable gt, goalnet_optim_opts o, const int64_t* __restrict__ step_dev,
+                                                          float gs, const double* __restrict__ sumsq, uint2* __restrict__ shadow, int64_t sh_b4,
                                                           int64_t sh_e4, int sh_f16, const int64_t* __restrict__ bad_step) {
-    const int64_t e = *step_dev, t1 = e + 1;              // t1: the step's own count, what goalnet_grad_finite_check stamps
-    if (bad_step && *bad_step == t1) return;
-    int r = 0;
-    while (r + 1 < nranges && (int)blockIdx.x >= rs.first_block[r + 1]) ++r;
-    const int64_t lb = (int)blockIdx.x - rs.first_block[r], nb = rs.first_block[r + 1] - rs.first_block[r];
-    const goalnet_group_hyper h = gt.h[rs.group[r]];
-    o.lr = h.lr;                                          // the schedule scales every group's own rate; min_lr is global
-    const double lr_t = sched_lr(o, e);
-    const AdamScalars sc = adam_scalars(lr_t, h.beta1, h.beta2, t1 - rs.skipped[r]);
-    ElemScalars s;
-    s.b2 = sc.b2; s.omb1 = sc.omb1; s.omb2 = sc.omb2; s.eps = (float)h.eps; s.step_size = sc.step_size; s.bc2_sqrt = sc.bc2_sqrt;
-    s.gs = gs;
-    s.coef = 1.0f;
-    if (sumsq) {                                          // one norm over all groups, as clip_grad_norm_ over all parameters
-        const double c = o.max_norm / ((double)gs * sqrt(*sumsq) + 1e-6);
-        s.coef = (float)(c < 1.0 ? c : 1.0);
-    }
-    s.wd = (float)h.weight_decay;
-    s.shrink = (float)(1.0 - lr_t * h.weight_decay);
-    const bool decay = ((rs.decay >> r) & 1u) != 0 && h.weight_decay > 0.0;
-    const int64_t begin = rs.begin[r], n = rs.count[r];
-    if (h.amsgrad)
-        range_dispatch<true>(decay, o.decoupled != 0, sumsq != nullptr, p, g, m, v, vmax, begin, n, lb, nb, s, shadow, sh_b4, sh_e4, sh_f16);
-    else
-        range_dispatch<false>(decay, o.decoupled != 0, sumsq != nullptr, p, g, m, v, nullptr, begin, n, lb, nb, s, shadow, sh_b4, sh_e4, sh_f16);
+    const int64_t e = *step_dev;                          // e + 1: the step's own count, what goalnet_grad_finite_check stamps
+    if (bad_step && *bad_step == e + 1) return;
+    const BlockShare b = block_share(rs, nranges);
+    const goalnet_group_hyper h = gt.h[st.group[b.r]];    // the schedule scales every group's own rate; min_lr is global
+    optim_block(p, g, m, v, vmax, b, st.skipped[b.r], ((st.decay >> b.r) & 1u) != 0, o, h.lr, h.beta1, h.beta2, h.eps, h.weight_decay,
+                h.amsgrad != 0, e, gs, sumsq, {shadow, sh_b4, sh_e4, sh_f16});
 }
 
 int check_group(const char* who, const goalnet_group_hyper& h, int k) {
@@ -79,10 +57,12 @@ int goalnet_group_step_dev_ranges(float* p, const float* g, float* m, float* v, 
                                   int f16, const int64_t* bad_step, void* stream) {
     const char* who = "group_step_dev_ranges";
     GN_REQUIRE(p && g && m && v && step && groups, GOALNET_E_NULL, "%s: null pointer", who);
-    GroupRanges rs;
-    int rc = check_ranges(who, ranges, count, OPTIM_BLOCKS_MAX, rs.begin, rs.count, rs.skipped, &rs.decay, rs.first_block);
-    if (rc != 0) return rc;
-    rc = check_opts(who, opts);
+    RangeMap rs;
+    GroupSteps st;
+    memset(&st, 0, sizeof st);                            // the entries beyond `count` too: no uninitialised bytes in a graph
+    int rc = map_ranges(who, ranges, count, RANGE_BLOCKS_MAX, &rs);
+    if (rc == 0) rc = copy_skipped(who, ranges, count, st.skipped);
+    if (rc == 0) rc = check_opts(who, opts);
     if (rc != 0) return rc;
     GN_REQUIRE(ngroups >= 1 && ngroups <= GOALNET_GROUPS_MAX, GOALNET_E_SHAPE, "%s: 1..%d groups", who, GOALNET_GROUPS_MAX);
     GroupTable gt;
@@ -94,18 +74,18 @@ int goalnet_group_step_dev_ranges(float* p, const float* g, float* m, float* v, 
     for (int r = 0; r < count; ++r) {
         GN_REQUIRE(ranges[r].group >= 0 && ranges[r].group < ngroups, GOALNET_E_SHAPE, "%s: range %d: group %d outside 0..%d", who, r,
                    ranges[r].group, ngroups - 1);
-        rs.group[r] = (uint8_t)ranges[r].group;
+        st.group[r] = (uint8_t)ranges[r].group;
+        st.decay |= (uint64_t)(ranges[r].decay != 0) << r;
         ams = ams || groups[ranges[r].group].amsgrad != 0;
     }
-    for (int r = count; r < GOALNET_ADAM_RANGES_MAX; ++r) rs.group[r] = 0;
     GN_REQUIRE(!ams || vmax, GOALNET_E_VALUE, "%s: a group with amsgrad needs the vmax arena", who);
     rc = check_step_args(who, p, g, m, v, opts, sumsq, shadow_16, shadow_begin, shadow_count);
     if (rc != 0) return rc;
     GN_REQUIRE(aligned16(vmax), GOALNET_E_ALIGN, "%s: arenas must be 16-byte aligned", who);
     hipLaunchKernelGGL(group_ranges_kernel, dim3((unsigned)rs.first_block[count]), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       ams ? vmax : nullptr, rs, count, gt, *opts, step, grad_scale, sumsq, (uint2*)shadow_16, shadow_begin >> 2,
+                       ams ? vmax : nullptr, rs, st, count, gt, *opts, step, grad_scale, sumsq, (uint2*)shadow_16, shadow_begin >> 2,
                        shadow_16 ? (shadow_begin + shadow_count) >> 2 : 0, f16, bad_step);
-    GN_LAUNCH_CHECK("group_step_dev_ranges");
+    GN_LAUNCH_CHECK(who);
     return 0;
 }
 
@@ -119,9 +99,7 @@ int goalnet_group_lr(const goalnet_optim_opts* opts, const goalnet_group_hyper* 
     if (rc != 0) return rc;
     goalnet_optim_opts o = *opts;
     o.lr = groups[g].lr;
-    hipLaunchKernelGGL(group_lr_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, o, step, lr_out);
-    GN_LAUNCH_CHECK("group_lr");
-    return 0;
+    return launch_sched_lr("group_lr", o, step, lr_out, stream);
 }
 
 }  // extern "C"

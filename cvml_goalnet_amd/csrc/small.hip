@@ -1,14 +1,9 @@
 // The small ops of the hot path: AudBl's two Conv1d layers, the 128 -> 1 head with Sigmoid and 4y+1,
-// the broadcast MSE loss, bias-gradient column sums, elementwise helpers and the fused Adam step.
-// /root/reference/utils.py:203-227 (AudBl), 255-256, 270 (head), main.py:68-70, 191-193 (loss, Adam).
+// the broadcast MSE loss, bias-gradient column sums and elementwise helpers (the fused Adam step is adam.hip's).
+// The reference's utils.py:203-227 (AudBl), 255-256, 270 (head), main.py:68-70 (loss).
 //
-// Together they are < 1 % of the model's arithmetic and, except Adam, touch
-// kilobytes to a few megabytes: they are written for correctness and determinism, not for a roofline.
-// Adam is the exception: one pass over the flat parameter arena at 28 B/parameter (HBM-bound), it was
-// 57 % of the reference's step at its own sub-batch size.
-#include <hip/hip_bf16.h>
-
-#include "adam.h"
+// Together they are < 1 % of the model's arithmetic and touch kilobytes to a few
+// megabytes: they are written for correctness and determinism, not for a roofline.
 #include "common.h"
 #include "mse.h"
 
@@ -390,122 +385,9 @@ __global__ __launch_bounds__(256) void mse_bcast_kernel(const float* __restrict_
     mse_bcast_block(pred, labels, N, loss, dpred);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam defaults, single-tensor operation order), one pass over the flat arena. The per-element update
-// (adam1) and the step's scalars (adam_scalars) live in adam.h: the weight-gradient GEMM's epilogue runs the same code.
-// ---------------------------------------------------------------------------------------------
-// four updated parameters as binary16 (f16 != 0) or bfloat16, packed for one 8-byte store into the 16-bit copy
-__device__ __forceinline__ uint2 pack4_16(const float4& pp, int f16) {
-    if (f16) {
-        const _Float16 a = (_Float16)pp.x, b = (_Float16)pp.y, c = (_Float16)pp.z, d = (_Float16)pp.w;
-        return make_uint2((unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16),
-                          (unsigned)__builtin_bit_cast(unsigned short, c) | ((unsigned)__builtin_bit_cast(unsigned short, d) << 16));
-    }
-    const __hip_bfloat16 a = __float2bfloat16(pp.x), b = __float2bfloat16(pp.y), c = __float2bfloat16(pp.z), d = __float2bfloat16(pp.w);
-    return make_uint2((unsigned)*reinterpret_cast<const unsigned short*>(&a) | ((unsigned)*reinterpret_cast<const unsigned short*>(&b) << 16),
-                      (unsigned)*reinterpret_cast<const unsigned short*>(&c) | ((unsigned)*reinterpret_cast<const unsigned short*>(&d) << 16));
-}
-
-// One kernel for both entry points (host step count / device step counter) so that they produce the same bits.
-// The scalars torch's _single_tensor_adam computes as python floats (doubles) are computed in fp64 here.
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, int64_t n, double lr, double beta1, double beta2,
-                                                  float eps, const int64_t* __restrict__ step_dev, int64_t step_host, float gs,
-                                                  uint2* __restrict__ shadow, int64_t sh_b4, int64_t sh_e4, int sh_f16,
-                                                  const int64_t* __restrict__ bad_step) {
-    const int64_t ti = step_dev ? *step_dev + step_host : step_host;               // device counter + bias, or the host count
-    // precision = "fp16": goalnet_grad_finite_check stamped this step as overflowed -> the whole update is skipped
-    if (bad_step && *bad_step == ti) return;
-    const AdamScalars sc = adam_scalars(lr, beta1, beta2, ti);
-    const float step_size = sc.step_size, bc2_sqrt = sc.bc2_sqrt, b2 = sc.b2, omb1 = sc.omb1, omb2 = sc.omb2;
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        const float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
-        adam1(pp.x, gg.x, mm.x, vv.x, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        adam1(pp.y, gg.y, mm.y, vv.y, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        adam1(pp.z, gg.z, mm.z, vv.z, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        adam1(pp.w, gg.w, mm.w, vv.w, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-        if (shadow && i >= sh_b4 && i < sh_e4) {       // 16-bit copy of the updated parameters of one slice (the next step's GEMM operand)
-            shadow[i - sh_b4] = pack4_16(pp, sh_f16);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = (n4 << 2) + threadIdx.x;
-        adam1(p[i], g[i], m[i], v[i], b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-    }
-}
-
-// The same update over up to GOALNET_ADAM_RANGES_MAX ranges of the arena in ONE launch (frozen tensors split the arena; a launch per
-// range would cost more than a small step saves). The descriptors travel by value in the kernel arguments, so a captured graph bakes
-// them. Blocks [first_block[r], first_block[r + 1]) serve range r and stride over it alone: no block spans two ranges. Range r runs
-// under its own step count *step + 1 - skipped[r] (torch.optim.Adam counts steps per parameter and skips those without a gradient);
-// element for element the arithmetic is adam_kernel's, so the result equals that kernel run range by range.
-struct AdamRanges {
-    int64_t begin[GOALNET_ADAM_RANGES_MAX], count[GOALNET_ADAM_RANGES_MAX], skipped[GOALNET_ADAM_RANGES_MAX];
-    int first_block[GOALNET_ADAM_RANGES_MAX + 1];
-};
-
-__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, AdamRanges rs, int nranges, double lr, double beta1,
-                                                         double beta2, float eps, const int64_t* __restrict__ step_dev, float gs,
-                                                         uint2* __restrict__ shadow, int64_t sh_b4, int64_t sh_e4, int sh_f16,
-                                                         const int64_t* __restrict__ bad_step) {
-    const int64_t t1 = *step_dev + 1;                     // the step's own count: what goalnet_grad_finite_check stamps
-    if (bad_step && *bad_step == t1) return;
-    int r = 0;
-    while (r + 1 < nranges && (int)blockIdx.x >= rs.first_block[r + 1]) ++r;
-    const int64_t lb = (int)blockIdx.x - rs.first_block[r], nb = rs.first_block[r + 1] - rs.first_block[r];
-    const AdamScalars sc = adam_scalars(lr, beta1, beta2, t1 - rs.skipped[r]);
-    const float step_size = sc.step_size, bc2_sqrt = sc.bc2_sqrt, b2 = sc.b2, omb1 = sc.omb1, omb2 = sc.omb2;
-    const int64_t begin = rs.begin[r], n = rs.count[r], b4 = begin >> 2, n4 = n >> 2;
-    for (int64_t j = lb * blockDim.x + threadIdx.x; j < n4; j += nb * blockDim.x) {
-        const int64_t i = b4 + j;                         // float4 index in the arena
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        const float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
-        adam1(pp.x, gg.x, mm.x, vv.x, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        adam1(pp.y, gg.y, mm.y, vv.y, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        adam1(pp.z, gg.z, mm.z, vv.z, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        adam1(pp.w, gg.w, mm.w, vv.w, b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-        if (shadow && i >= sh_b4 && i < sh_e4) shadow[i - sh_b4] = pack4_16(pp, sh_f16);
-    }
-    if (lb == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = begin + (n4 << 2) + threadIdx.x;
-        adam1(p[i], g[i], m[i], v[i], b2, omb1, omb2, eps, step_size, bc2_sqrt, gs);
-    }
-}
-
 // x *= s (the loss scale of precision = "fp16" on dL/dpred)
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, int64_t n, float s) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) x[i] *= s;
-}
-
-// any non-finite value in g -> *bad_step = max(*bad_step, this step's 1-based count): the fused Adam of this step then returns
-// without touching anything (adam_kernel); any number of blocks may write. The step's last launch
-// (goalnet_counters_add4_guarded, stepstate.hip) keeps the step count where it is for a stamped step and clears the stamp.
-__global__ __launch_bounds__(256) void grad_finite_check_kernel(const float* __restrict__ g, int64_t n, const int64_t* __restrict__ step,
-                                                               int64_t step_bias, int64_t* __restrict__ bad_step,
-                                                               int64_t* __restrict__ skipped) {
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = g[i];
-        bad |= (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;       // inf or nan: exponent all ones (FLT_MAX is finite)
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) {
-        const unsigned long long t = (unsigned long long)(*step + step_bias);
-        const unsigned long long old = atomicMax(reinterpret_cast<unsigned long long*>(bad_step), t);
-        if (old != t && skipped) atomicAdd(reinterpret_cast<unsigned long long*>(skipped), 1ull);       // first reporter of this step
-    }
 }
 
 unsigned grid1d(int64_t n, int cap = 4096) {
@@ -653,116 +535,12 @@ int goalnet_mse_bcast(const float* pred, const float* labels, int N, float* loss
     return 0;
 }
 
-static int adam_launch(const char* who, float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
-                       double beta2, double eps, const int64_t* step_dev, int64_t step_host, float grad_scale, void* stream,
-                       void* shadow = nullptr, int64_t sh_begin = 0, int64_t sh_count = 0, int sh_f16 = 0, const int64_t* bad_step = nullptr,
-                       int max_blocks = 8192) {
-    GN_REQUIRE(p && g && m && v, GOALNET_E_NULL, "%s: null pointer", who);
-    GN_REQUIRE(n > 0, GOALNET_E_SHAPE, "%s: bad count", who);
-    GN_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), GOALNET_E_ALIGN, "%s: arenas must be 16-byte aligned", who);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n >> 2, max_blocks)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2,
-                       (float)eps, step_dev, step_host, grad_scale, (uint2*)shadow, sh_begin >> 2, (sh_begin + sh_count) >> 2, sh_f16, bad_step);
-    GN_LAUNCH_CHECK(who);
-    return 0;
-}
-
-/* goalnet_adam_step_dev on at most max_blocks blocks of 256 threads: a BACKGROUND pass. The 10-frame step runs the update of
- * linear5.weight (90 % of the bytes) on its own stream under the rest of backward; on the default 8192 blocks it takes every CU and
- * all of the HBM bandwidth and the latency-bound kernels of the backward chain queue behind it, on ~128 blocks it streams at a
- * third of the bandwidth and leaves the chain alone. */
-int goalnet_adam_step_dev_blocks(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                                 double eps, const int64_t* step, int64_t step_bias, float grad_scale, int max_blocks, void* stream) {
-    GN_REQUIRE(step, GOALNET_E_NULL, "adam_step_dev_blocks: null pointer");
-    GN_REQUIRE(max_blocks >= 1 && max_blocks <= 65535, GOALNET_E_SHAPE, "adam_step_dev_blocks: 1..65535 blocks");
-    return adam_launch("adam_step_dev_blocks", p, g, m, v, n, lr, beta1, beta2, eps, step, step_bias, grad_scale, stream, nullptr, 0, 0, 0, nullptr,
-                       max_blocks);
-}
-
-int goalnet_adam_step_dev_shadow(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                                 double eps, const int64_t* step, int64_t step_bias, float grad_scale, void* shadow_bf16,
-                                 int64_t shadow_begin, int64_t shadow_count, int f16, void* stream) {
-    GN_REQUIRE(step && shadow_bf16, GOALNET_E_NULL, "adam_step_dev_shadow: null pointer");
-    GN_REQUIRE(shadow_begin >= 0 && shadow_count > 0 && shadow_begin + shadow_count <= n && (shadow_begin & 3) == 0 && (shadow_count & 3) == 0,
-               GOALNET_E_SHAPE, "adam_step_dev_shadow: the shadowed slice must lie inside the arena, offset and length multiples of 4");
-    GN_REQUIRE((reinterpret_cast<uintptr_t>(shadow_bf16) & 7u) == 0, GOALNET_E_ALIGN, "adam_step_dev_shadow: shadow must be 8-byte aligned");
-    return adam_launch("adam_step_dev_shadow", p, g, m, v, n, lr, beta1, beta2, eps, step, step_bias, grad_scale, stream, shadow_bf16,
-                       shadow_begin, shadow_count, f16);
-}
-
-/* precision = "fp16" (loss-scaled gradients): the same two entry points with an overflow guard — the update is skipped when
- * goalnet_grad_finite_check stamped this step (*bad_step == *step + step_bias). shadow may be NULL. */
-int goalnet_adam_step_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                                  double eps, const int64_t* step, int64_t step_bias, float grad_scale, void* shadow_16,
-                                  int64_t shadow_begin, int64_t shadow_count, int f16, const int64_t* bad_step, void* stream) {
-    GN_REQUIRE(step && bad_step, GOALNET_E_NULL, "adam_step_dev_guarded: null pointer");
-    if (shadow_16) {
-        GN_REQUIRE(shadow_begin >= 0 && shadow_count > 0 && shadow_begin + shadow_count <= n && (shadow_begin & 3) == 0 && (shadow_count & 3) == 0,
-                   GOALNET_E_SHAPE, "adam_step_dev_guarded: the shadowed slice must lie inside the arena, offset and length multiples of 4");
-        GN_REQUIRE((reinterpret_cast<uintptr_t>(shadow_16) & 7u) == 0, GOALNET_E_ALIGN, "adam_step_dev_guarded: shadow must be 8-byte aligned");
-    }
-    return adam_launch("adam_step_dev_guarded", p, g, m, v, n, lr, beta1, beta2, eps, step, step_bias, grad_scale, stream, shadow_16,
-                       shadow_begin, shadow_16 ? shadow_count : 0, f16, bad_step);
-}
-
-/* goalnet_adam_step_dev[_guarded] over a list of arena ranges in one launch; range r runs under the count *step + 1 - skipped[r] */
-int goalnet_adam_step_dev_ranges(float* p, const float* g, float* m, float* v, const goalnet_adam_range* ranges, int count, double lr,
-                                 double beta1, double beta2, double eps, const int64_t* step, float grad_scale, void* shadow_16,
-                                 int64_t shadow_begin, int64_t shadow_count, int f16, const int64_t* bad_step, void* stream) {
-    GN_REQUIRE(p && g && m && v && ranges && step, GOALNET_E_NULL, "adam_step_dev_ranges: null pointer");
-    GN_REQUIRE(count >= 1 && count <= GOALNET_ADAM_RANGES_MAX, GOALNET_E_SHAPE, "adam_step_dev_ranges: 1..%d ranges", GOALNET_ADAM_RANGES_MAX);
-    GN_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), GOALNET_E_ALIGN, "adam_step_dev_ranges: arenas must be 16-byte aligned");
-    AdamRanges rs;
-    int64_t end = 0;
-    rs.first_block[0] = 0;
-    for (int r = 0; r < count; ++r) {
-        const goalnet_adam_range& a = ranges[r];
-        GN_REQUIRE(a.begin >= 0 && a.count > 0, GOALNET_E_SHAPE, "adam_step_dev_ranges: range %d is empty or starts below 0", r);
-        GN_REQUIRE(a.skipped >= 0, GOALNET_E_SHAPE, "adam_step_dev_ranges: range %d: negative count of skipped steps", r);
-        GN_REQUIRE((a.begin & 3) == 0, GOALNET_E_ALIGN, "adam_step_dev_ranges: range %d must begin at a multiple of 4 elements", r);
-        GN_REQUIRE(a.begin >= end, GOALNET_E_SHAPE, "adam_step_dev_ranges: range %d overlaps its predecessor or is out of order", r);
-        end = a.begin + a.count;
-        rs.begin[r] = a.begin; rs.count[r] = a.count; rs.skipped[r] = a.skipped;
-        rs.first_block[r + 1] = rs.first_block[r] + (int)grid1d(a.count >> 2, 8192);
-    }
-    if (shadow_16) {
-        GN_REQUIRE(shadow_begin >= 0 && shadow_count > 0 && (shadow_begin & 3) == 0 && (shadow_count & 3) == 0, GOALNET_E_SHAPE,
-                   "adam_step_dev_ranges: the shadowed slice's offset and length must be multiples of 4");
-        GN_REQUIRE((reinterpret_cast<uintptr_t>(shadow_16) & 7u) == 0, GOALNET_E_ALIGN, "adam_step_dev_ranges: shadow must be 8-byte aligned");
-    }
-    hipLaunchKernelGGL(adam_ranges_kernel, dim3((unsigned)rs.first_block[count]), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rs, count, lr,
-                       beta1, beta2, (float)eps, step, grad_scale, (uint2*)shadow_16, shadow_begin >> 2,
-                       shadow_16 ? (shadow_begin + shadow_count) >> 2 : 0, f16, bad_step);
-    GN_LAUNCH_CHECK("adam_step_dev_ranges");
-    return 0;
-}
-
 int goalnet_scale(float* x, int64_t n, float s, void* stream) {
     GN_REQUIRE(x, GOALNET_E_NULL, "scale: null pointer");
     GN_REQUIRE(n > 0, GOALNET_E_SHAPE, "scale: bad count");
     hipLaunchKernelGGL(scale_kernel, dim3(grid1d(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, n, s);
     GN_LAUNCH_CHECK("scale");
     return 0;
-}
-
-int goalnet_grad_finite_check(const float* g, int64_t n, const int64_t* step, int64_t step_bias, int64_t* bad_step, int64_t* skipped,
-                              void* stream) {
-    GN_REQUIRE(g && step && bad_step, GOALNET_E_NULL, "grad_finite_check: null pointer");
-    GN_REQUIRE(n > 0, GOALNET_E_SHAPE, "grad_finite_check: bad count");
-    hipLaunchKernelGGL(grad_finite_check_kernel, dim3(grid1d(n, 1024)), dim3(256), 0, (hipStream_t)stream, g, n, step, step_bias, bad_step, skipped);
-    GN_LAUNCH_CHECK("grad_finite_check");
-    return 0;
-}
-
-int goalnet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
-                      double beta2, double eps, int step, float grad_scale, void* stream) {
-    GN_REQUIRE(step >= 1, GOALNET_E_SHAPE, "adam_step: step is 1-based");
-    return adam_launch("adam_step", p, g, m, v, n, lr, beta1, beta2, eps, nullptr, step, grad_scale, stream);
-}
-
-int goalnet_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                          double eps, const int64_t* step, int64_t step_bias, float grad_scale, void* stream) {
-    GN_REQUIRE(step, GOALNET_E_NULL, "adam_step_dev: null step counter");
-    return adam_launch("adam_step_dev", p, g, m, v, n, lr, beta1, beta2, eps, step, step_bias, grad_scale, stream);
 }
 
 }  // extern "C"

@@ -995,31 +995,35 @@ def adam_step_dev_guarded(p, g, m, v, lr, beta1, beta2, eps, step, bad_step, sha
                                               0 if shadow is None else _f16(shadow), _ctr(bad_step), _s()), "adam_step_dev_guarded")
 
 
+def _ranges(who, ranges, n, struct):
+    """[(begin, count[, skipped[, decay[, group]]])] inside an arena of n elements -> struct[]; the fields a tuple leaves out are 0"""
+    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"{who}: 1..{_lib.ADAM_RANGES_MAX} ranges")
+    _req(all(r[0] >= 0 and r[1] > 0 and r[0] + r[1] <= n for r in ranges), f"{who}: a range leaves the arena")
+    rows = [[int(bool(x)) if i == 3 else int(x) for i, x in enumerate(r)] for r in ranges]          # field 3, `decay`, is a flag
+    return (struct * len(rows))(*[struct(*f) for f in rows])
+
+
+def _shadow_tail(who, shadow, shadow_begin, n, bad_step):
+    """the checked last arguments of the update launches over ranges: (shadow, begin, count, f16, bad_step, stream)"""
+    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
+         f"{who}: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
+    return (_p(shadow), int(shadow_begin), 0 if shadow is None else shadow.numel(), 0 if shadow is None else _f16(shadow),
+            0 if bad_step is None else _ctr(bad_step), _s())
+
+
 def adam_step_dev_ranges(p, g, m, v, ranges, lr, beta1, beta2, eps, step, grad_scale=1.0, shadow=None, shadow_begin=0, bad_step=None):
     """adam_step_dev[_guarded] over `ranges` = [(begin, count, skipped)] of the arenas p, g, m, v in ONE launch; a range's 1-based step
     count is *step + 1 - skipped. `shadow` (16-bit) receives the updated arena[shadow_begin : shadow_begin + shadow.numel()]."""
     _chk(p, g, m, v, shadow)
     n = p.numel()
     _req(g.numel() == n and m.numel() == n and v.numel() == n, "adam_step_dev_ranges: p, g, m, v must have the same size")
-    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"adam_step_dev_ranges: 1..{_lib.ADAM_RANGES_MAX} ranges")
-    _req(all(b >= 0 and c > 0 and b + c <= n for b, c, _ in ranges), "adam_step_dev_ranges: a range leaves the arena")
-    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
-         "adam_step_dev_ranges: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
-    arr = (_lib.AdamRange * len(ranges))(*[_lib.AdamRange(int(b), int(c), int(k)) for b, c, k in ranges])
+    arr = _ranges("adam_step_dev_ranges", ranges, n, _lib.AdamRange)
+    tail = _shadow_tail("adam_step_dev_ranges", shadow, shadow_begin, n, bad_step)
     check(lib().goalnet_adam_step_dev_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), arr, len(ranges), lr, beta1, beta2, eps,
-                                             _ctr(step), grad_scale, _p(shadow), int(shadow_begin), 0 if shadow is None else shadow.numel(),
-                                             0 if shadow is None else _f16(shadow), 0 if bad_step is None else _ctr(bad_step), _s()),
-          "adam_step_dev_ranges")
+                                             _ctr(step), grad_scale, *tail), "adam_step_dev_ranges")
 
 
 # ---- optimizer options on the fused step (include/goalnet_optim.h, DESIGN.md §4.14) ----
-def _optim_ranges(who, ranges, n):
-    """[(begin, count, skipped, decay)] -> goalnet_optim_range[]"""
-    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"{who}: 1..{_lib.ADAM_RANGES_MAX} ranges")
-    _req(all(b >= 0 and c > 0 and b + c <= n for b, c, _, _ in ranges), f"{who}: a range leaves the arena")
-    return (_lib.OptimRange * len(ranges))(*[_lib.OptimRange(int(b), int(c), int(k), int(bool(d)), 0) for b, c, k, d in ranges])
-
-
 def _optim_opts(lr, beta1, beta2, eps, optim):
     """the host structure of one launch: base rate and betas of the call, everything else from the OptimOptions"""
     return _lib.OptimOpts(float(lr), float(beta1), float(beta2), float(eps), float(optim.weight_decay),
@@ -1033,7 +1037,7 @@ def grad_sumsq(g, ranges, out=None):
     fixed shares and a fixed order, so the same data gives the same bits"""
     _chk(g, out)
     _req(g.dtype == F32 and g.is_contiguous(), "grad_sumsq: g must be a contiguous fp32 arena")
-    arr = _optim_ranges("grad_sumsq", ranges, g.numel())
+    arr = _ranges("grad_sumsq", ranges, g.numel(), _lib.OptimRange)
     if out is None:
         out = torch.empty(1, dtype=torch.float64, device=g.device)
     _req(out.dtype == torch.float64 and out.numel() == 1, "grad_sumsq: out must be one float64")
@@ -1052,16 +1056,13 @@ def optim_step_dev_ranges(p, g, m, v, ranges, lr, beta1, beta2, eps, optim, step
     _chk(p, g, m, v, shadow, sumsq)
     n = p.numel()
     _req(g.numel() == n and m.numel() == n and v.numel() == n, "optim_step_dev_ranges: p, g, m, v must have the same size")
-    arr = _optim_ranges("optim_step_dev_ranges", ranges, n)
+    arr = _ranges("optim_step_dev_ranges", ranges, n, _lib.OptimRange)
     _req((sumsq is None) == (optim.max_grad_norm is None), "optim_step_dev_ranges: sumsq goes with max_grad_norm, and only with it")
     _req(sumsq is None or (sumsq.dtype == torch.float64 and sumsq.numel() == 1), "optim_step_dev_ranges: sumsq must be one float64")
-    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
-         "optim_step_dev_ranges: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
+    tail = _shadow_tail("optim_step_dev_ranges", shadow, shadow_begin, n, bad_step)
     opts = _optim_opts(lr, beta1, beta2, eps, optim)
     check(lib().goalnet_optim_step_dev_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), arr, len(ranges), ctypes.byref(opts),
-                                              _ctr(step), grad_scale, _p(sumsq), _p(shadow), int(shadow_begin),
-                                              0 if shadow is None else shadow.numel(), 0 if shadow is None else _f16(shadow),
-                                              0 if bad_step is None else _ctr(bad_step), _s()), "optim_step_dev_ranges")
+                                              _ctr(step), grad_scale, _p(sumsq), *tail), "optim_step_dev_ranges")
 
 
 def optim_lr(lr, optim, step, out=None):
@@ -1097,20 +1098,14 @@ def group_step_dev_ranges(p, g, m, v, vmax, ranges, table, optim, step, grad_sca
     _req(g.numel() == n and m.numel() == n and v.numel() == n, "group_step_dev_ranges: p, g, m, v must have the same size")
     _req(vmax is None or (vmax.dtype == F32 and vmax.is_contiguous() and vmax.numel() == n),
          "group_step_dev_ranges: vmax must be a contiguous fp32 arena of the size of v")
-    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"group_step_dev_ranges: 1..{_lib.ADAM_RANGES_MAX} ranges")
-    _req(all(b >= 0 and c > 0 and b + c <= n for b, c, _, _, _ in ranges), "group_step_dev_ranges: a range leaves the arena")
-    arr = (_lib.GroupRange * len(ranges))(*[_lib.GroupRange(int(b), int(c), int(k), int(bool(d)), int(q)) for b, c, k, d, q in ranges])
+    arr = _ranges("group_step_dev_ranges", ranges, n, _lib.GroupRange)
     tab = _group_table("group_step_dev_ranges", table)
     _req((sumsq is None) == (optim.max_grad_norm is None), "group_step_dev_ranges: sumsq goes with max_grad_norm, and only with it")
     _req(sumsq is None or (sumsq.dtype == torch.float64 and sumsq.numel() == 1), "group_step_dev_ranges: sumsq must be one float64")
-    _req(shadow is None or (shadow.dtype in H16 and shadow.is_contiguous() and shadow_begin + shadow.numel() <= n),
-         "group_step_dev_ranges: shadow must be a contiguous 16-bit tensor for a slice inside the arena")
+    tail = _shadow_tail("group_step_dev_ranges", shadow, shadow_begin, n, bad_step)
     opts = _optim_opts(table[0][0], table[0][1], table[0][2], table[0][3], optim)
     check(lib().goalnet_group_step_dev_ranges(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), arr, len(ranges), tab,
-                                              len(table), ctypes.byref(opts), _ctr(step), grad_scale, _p(sumsq), _p(shadow),
-                                              int(shadow_begin), 0 if shadow is None else shadow.numel(),
-                                              0 if shadow is None else _f16(shadow), 0 if bad_step is None else _ctr(bad_step), _s()),
-          "group_step_dev_ranges")
+                                              len(table), ctypes.byref(opts), _ctr(step), grad_scale, _p(sumsq), *tail), "group_step_dev_ranges")
 
 
 def group_lr(table, group, optim, step, out=None):
@@ -1128,13 +1123,7 @@ def group_lr(table, group, optim, step, out=None):
 
 
 # ---- the weight average behind the fused step (include/goalnet_ema.h, DESIGN.md §4.15) ----
-def _plain_ranges(who, ranges, n):
-    """[(begin, count)] or [(begin, count, skipped)] -> goalnet_adam_range[] (the count of sat-out steps is not read)"""
-    _req(1 <= len(ranges) <= _lib.ADAM_RANGES_MAX, f"{who}: 1..{_lib.ADAM_RANGES_MAX} ranges")
-    _req(all(r[0] >= 0 and r[1] > 0 and r[0] + r[1] <= n for r in ranges), f"{who}: a range leaves the arena")
-    return (_lib.AdamRange * len(ranges))(*[_lib.AdamRange(int(r[0]), int(r[1]), 0) for r in ranges])
-
-
+# ranges = [(begin, count)] or [(begin, count, skipped)]: these passes do not read the count of sat-out steps, and it is not handed on
 def ema_update_dev_ranges(p, e, ranges, ema, step, step_bias=1, bad_step=None):
     """the average `e` of the weights `p` over `ranges` in ONE launch, under `ema` (optim.EmaOptions) at the 1-based step count
     t = *step + step_bias: a copy up to ema.start_step, then every ema.every-th step e += w (p - e) with w = ema.weight_at(t); a step
@@ -1143,7 +1132,7 @@ def ema_update_dev_ranges(p, e, ranges, ema, step, step_bias=1, bad_step=None):
     n = p.numel()
     _req(p.dtype == F32 and e.dtype == F32 and p.is_contiguous() and e.is_contiguous() and e.numel() == n,
          "ema_update_dev_ranges: p and e must be contiguous fp32 arenas of one size")
-    arr = _plain_ranges("ema_update_dev_ranges", ranges, n)
+    arr = _ranges("ema_update_dev_ranges", [r[:2] for r in ranges], n, _lib.AdamRange)
     opts = _lib.EmaOpts(float(ema.decay), int(ema.every), int(ema.start_step), int(bool(ema.warmup)), 0)
     check(lib().goalnet_ema_update_dev_ranges(p.data_ptr(), e.data_ptr(), arr, len(ranges), ctypes.byref(opts), _ctr(step), int(step_bias),
                                               0 if bad_step is None else _ctr(bad_step), _s()), "ema_update_dev_ranges")
@@ -1155,7 +1144,7 @@ def swap_ranges(a, b, ranges):
     n = a.numel()
     _req(a.dtype == F32 and b.dtype == F32 and a.is_contiguous() and b.is_contiguous() and b.numel() == n,
          "swap_ranges: a and b must be contiguous fp32 arenas of one size")
-    arr = _plain_ranges("swap_ranges", ranges, n)
+    arr = _ranges("swap_ranges", [r[:2] for r in ranges], n, _lib.AdamRange)
     check(lib().goalnet_swap_ranges(a.data_ptr(), b.data_ptr(), arr, len(ranges), _s()), "swap_ranges")
 
 
@@ -1167,7 +1156,7 @@ def grad_accum_dev_ranges(acc, g, ranges, scale, first):
     n = g.numel()
     _req(acc.dtype == F32 and g.dtype == F32 and acc.is_contiguous() and g.is_contiguous() and acc.numel() == n,
          "grad_accum_dev_ranges: acc and g must be contiguous fp32 arenas of one size")
-    arr = _plain_ranges("grad_accum_dev_ranges", ranges, n)
+    arr = _ranges("grad_accum_dev_ranges", [r[:2] for r in ranges], n, _lib.AdamRange)
     check(lib().goalnet_grad_accum_dev_ranges(acc.data_ptr(), g.data_ptr(), arr, len(ranges), float(scale), int(bool(first)), _s()),
           "grad_accum_dev_ranges")
 

@@ -5,7 +5,7 @@ parameter arena instead of torch's per-tensor passes over 30 strided views.
     optimizer.zero_grad(); loss.backward(); optimizer.step()                   # main.py:187-193, unchanged
 
 Same defaults and the same arithmetic as torch's single-tensor Adam (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad,
-bias-corrected; `goalnet_adam_step_dev`, csrc/small.hip). The parameters must be those of ONE `AVM` (they are views of its arena, and
+bias-corrected; `goalnet_adam_step_dev`, csrc/adam.hip). The parameters must be those of ONE `AVM` (they are views of its arena, and
 autograd leaves their gradients in its gradient arena: `_AVMFunction.backward`); like the stock optimizer it may be constructed before
 the first forward (Lazy parameters). Parameters with `requires_grad=False` are left alone, moments and step count included (pass all
 parameters or only the trainable ones). `zero_grad()` only drops the `.grad` references: the gradient arena is overwritten by every

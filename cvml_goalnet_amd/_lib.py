@@ -31,6 +31,12 @@ class RowCopyIndexed(ctypes.Structure):
                 ("cursor_bias", c_int64), ("indexed", c_int), ("table_rows", c_int64)]
 
 
+class RowMix(ctypes.Structure):
+    """goalnet_rowmix (include/goalnet_mix.h)"""
+    _fields_ = [("table", c_void_p), ("dst", c_void_p), ("row_elems", c_int64), ("nrows", c_int), ("cursor", c_void_p), ("cursor_bias", c_int64),
+                ("table_rows", c_int64)]
+
+
 class AdamRange(ctypes.Structure):
     """goalnet_adam_range (include/goalnet_hip.h)"""
     _fields_ = [("begin", c_int64), ("count", c_int64), ("skipped", c_int64)]
@@ -260,6 +266,18 @@ GROUPS_PROTOTYPES = {
 }
 GROUPS_MAX = 8            # GOALNET_GROUPS_MAX
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_mix.h, the eighth public header (audio
+# augmentation and mixup on a shuffled / augmented pass): additions, the tables above stay as they are
+MIX_PROTOTYPES = {
+    "goalnet_epoch_plan2": (c_int, [P, P, c_int, c_uint64, c_uint32, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P]),
+    "goalnet_audio_gather_aug": (c_int, [P, c_int64, P, P, P, c_int, c_int, c_int, c_int, P, c_int64, c_int, c_float, P]),
+    "goalnet_frames_gather_mix": (c_int, [P, c_int64, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int, P]),
+    "goalnet_rows_mix_indexed": (c_int, [ctypes.POINTER(RowMix), c_int, P, P, c_int, P]),
+}
+PLAN2_WORDS = 12          # GOALNET_PLAN2_WORDS
+PLAN2_MAX_INDEX = 1 << 26  # GOALNET_PLAN2_MAX_INDEX
+AUDIO_GAIN, AUDIO_NOISE, AUDIO_MIX = 1, 2, 4      # GOALNET_AUDIO_*
+
 _lib = None
 
 
@@ -278,7 +296,7 @@ def load():
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
-                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items()):
+                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items(), *MIX_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -42,6 +42,11 @@ applied at the end of the video (`accum_windows`). The graph key carries the pha
 
 EXTENSION (off by default): `shuffle=True` / `augment={...}` draw a plan per pass on the device — frame order, flip,
 shift, contrast, brightness per frame — and the same graphs gather their sub-batches through it; predictions come back in frame order.
+
+EXTENSION (off by default): `audio_augment={...}` / `mixup={...}` draw a second table beside that plan — per frame a
+time shift, a time mask, a coefficient mask, a gain and a noise key for its audio row, and a mixup partner with its weight — and the
+same graphs gather audio, frames, labels and loss weights through both. Under mixup a frame's prediction is the model's output on
+the MIXED input; `eval_video` never augments.
 """
 from __future__ import annotations
 
@@ -66,7 +71,7 @@ def _plain(x):
 class VideoTrainer:
     def __init__(self, model, subbatch_size: int = 10, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  graphs: bool = True, loss: str = "mse_bcast", loss_param=None, shuffle: bool = False, augment=None,
-                 seed: int = synth.BASE_SEED, optim=None, ema=None, accumulate: int = 1):
+                 seed: int = synth.BASE_SEED, optim=None, ema=None, accumulate: int = 1, audio_augment=None, mixup=None):
         if subbatch_size < 1:
             raise ValueError("subbatch_size must be >= 1")
         # EXTENSION: sub-batches per optimizer step. 1: train_step is called as before.
@@ -93,7 +98,18 @@ class VideoTrainer:
         self.passes = 0                                         # train_video calls so far = the pass index of the next plan
         self._colour = self.augment["contrast"] > 0 or self.augment["brightness"] > 0
         self._augments = self._colour or self.augment["flip_p"] > 0 or self.augment["max_shift"] > 0
-        self._planned = self.shuffle or self._augments          # sub-batches go through the plan
+        # EXTENSION: audio augmentation and mixup, drawn into a second table beside the plan. Absent, None or all
+        # zero: nothing below changes what _sub_step launches.
+        self.audio_augment = _augment.audio_augment_options(audio_augment)      # ValueError: unknown option, value out of range
+        self.mixup = _augment.mixup_options(mixup)
+        self._audio_aug = any(v > 0 for v in self.audio_augment.values())
+        self._mix = self.mixup["strength"] > 0 and self.mixup["p"] > 0
+        if self._audio_aug and not model.audio_included:
+            raise ValueError("audio_augment needs a model with audio_included=True")
+        if self._mix and model.head == "classifier":
+            raise ValueError("mixup blends labels: it needs the regression head (class labels cannot be blended)")
+        self._mix_sig = (tuple(self.audio_augment.items()), tuple(self.mixup.items())) if (self._audio_aug or self._mix) else ()
+        self._planned = self.shuffle or self._augments or bool(self._mix_sig)      # sub-batches go through the plan
         ops.loss_spec(loss, loss_param, False, model.head)      # ValueError: unknown name, beta <= 0, the classifier head
         self.loss, self.loss_param = loss, loss_param           # AVM.train_step's loss; the default is the reference's
         self._weighted = False                                  # the video being trained on came with per-frame weights
@@ -101,7 +117,7 @@ class VideoTrainer:
         self.subbatch_size = subbatch_size          # main.py:44
         self.lr, self.betas, self.eps = lr, betas, eps
         self.graphs = graphs
-        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, ema signature, accumulation phase, training) -> graph
+        self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}        # (sub-batch size, loss scale, trainable ranges, loss, (shuffle, colour, augments), optim signature, ema signature, accumulation phase, (audio_augment, mixup) signatures, training) -> graph
         self._uses_w5b: Dict[tuple, bool] = {}      # that graph reads the bf16 copy of linear5.weight (precision="bf16", n > 16)
         self._shadows: Dict[tuple, bool] = {}       # that graph's fused Adam refreshes the copy (it was live at capture)
         self._seen = set()
@@ -134,6 +150,8 @@ class VideoTrainer:
         self._loss = torch.empty((cap + sb - 1) // sb + 1, dtype=F32, device=dev)
         # the pass plan (augment.py): rewritten eagerly by every train_video, read by the graphs at this address
         self._plan = torch.zeros(cap, 8, dtype=torch.int32, device=dev) if self._planned else None
+        # its second table, rewritten and read the same way
+        self._plan2 = torch.zeros(cap, 12, dtype=torch.int32, device=dev) if self._mix_sig else None
 
     def _step_kw(self):
         """train_step's keyword arguments beyond the loss: optimizer options, weight average, and — inside a window of more than one
@@ -181,12 +199,19 @@ class VideoTrainer:
         m = self.model
         st = m._state
         dev = m._device
-        ops.frames_gather_aug(self._vid, vis, self._plan, n, st[2], 0, self._colour)
+        if self._mix:
+            ops.frames_gather_mix(self._vid, vis, self._plan, self._plan2, n, st[2], 0, self._colour)
+        else:
+            ops.frames_gather_aug(self._vid, vis, self._plan, n, st[2], 0, self._colour)
         segs = [(self._lab, lab, n, st[2], 0, True, True)]
         aud = None
         if m.audio_included:
             aud = torch.empty(n, 30, self._key[1], dtype=F32, device=dev)
-            segs.append((self._aud, aud, n, st[2], 0, True, True))
+            if self._mix_sig:       # the audio rows through both tables, in a launch of their own
+                ops.audio_gather_aug(self._aud, aud, self._plan, self._plan2, n, st[2], 0, gain=self.audio_augment["gain"] > 0,
+                                     noise=self.audio_augment["noise"], mix=self._mix)
+            else:
+                segs.append((self._aud, aud, n, st[2], 0, True, True))
         lkw = {}
         if self.loss != "mse_bcast":
             wts = None
@@ -194,7 +219,10 @@ class VideoTrainer:
                 wts = torch.empty(n, dtype=F32, device=dev)
                 segs.append((self._wts, wts, n, st[2], 0, True, True))
             lkw = dict(loss=self.loss, loss_param=self.loss_param, weights=wts)
-        ops.rows_copy_indexed(segs, self._plan)
+        if self._mix:               # labels and weights are blended like the inputs
+            ops.rows_mix_indexed([s[:5] for s in segs], self._plan, self._plan2)
+        else:
+            ops.rows_copy_indexed(segs, self._plan)
         # the step's last launch moves the counters; the results are then written at the positions the step started from
         loss, pred = m.train_step(aud, vis, lab, self.lr, self.betas, self.eps, _loop_tick=(n, 1), **lkw, **self._step_kw())
         if m.head == "classifier":
@@ -238,8 +266,10 @@ class VideoTrainer:
         # when off. Which steps copy, average or pass is decided inside replays, from the device step counter.
         # Accumulation: whether the micro-step overwrites or adds to the accumulator, whether it updates, and 1 / length
         # are baked into the launches, so the phase (first?, last?, length) is k[7]; (True, True, 1) without accumulation.
+        # Audio augmentation / mixup: which gathers the graph holds, their flags and the noise amplitude are launch
+        # arguments, so the two option signatures are k[8], () when both are off; the draws live in the second plan table.
         gkey = (n, m._loss_scale_for(n), m.trainable_signature(), (self.loss, self.loss_param, self._weighted),
-                (self.shuffle, self._colour, self._augments), self._optim_sig, self._ema_sig, self._phase, m.training)
+                (self.shuffle, self._colour, self._augments), self._optim_sig, self._ema_sig, self._phase, self._mix_sig, m.training)
         g = self._graphs.get(gkey)
         if g is not None and self._uses_w5b.get(gkey) and m._w5b_version != m._w5_version():
             # the captured graph reads the bf16 copy of linear5.weight and keeps it fresh through its own fused Adam, but holds
@@ -290,6 +320,8 @@ class VideoTrainer:
         # (windows end with the video, so a state taken between two videos needs nothing about them; "accumulate" is listed only when
         # on, which keeps a default trainer's state what it was)
         acc = {} if self.accumulate == 1 else {"accumulate": self.accumulate}
+        if self._mix_sig:       # listed only when on, as "accumulate" is
+            acc["plan2"] = self._mix_sig
         return {**acc, "loss": (self.loss, self.loss_param), "plan": (self.shuffle, tuple(sorted(self.augment.items()))),
                 "optim": self._optim_sig, "ema": self._ema_sig, "subbatch_size": self.subbatch_size,
                 "step": (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps))}
@@ -356,10 +388,21 @@ class VideoTrainer:
         batch_labels (N,), weights (N,) float32 or None (the trainer's pointwise losses) — CPU or GPU tensors.
         Returns (losses (S,), predictions (N,)) as GPU tensors with S = ceil(N / subbatch_size); nothing has been synchronised. `losses.mean()` is main.py:203's batch_loss.
         With shuffle / augment on, the pass follows the plan of index `self.passes` (or `plan_index`, to resume a run): sub-batch s
-        holds the frames plan[s * sb : (s + 1) * sb] names, `losses` is in sub-batch order and `predictions` in FRAME order."""
+        holds the frames plan[s * sb : (s + 1) * sb] names, `losses` is in sub-batch order and `predictions` in FRAME order.
+        With audio_augment / mixup on, a second table of the same pass index carries the audio draws and the mixup partners
+        (DESIGN.md §4.18). Under mixup `predictions[src_i]` is the model's output on the MIXED input of frame src_i — lambda of its
+        own sample plus 1 - lambda of its partner's —, not on the frame itself: use `eval_video`, which never augments, for
+        predictions of the video. ValueError, before anything is launched, if audio_augment's time_mask exceeds the audio bins."""
         if plan_index is not None and (isinstance(plan_index, bool) or not isinstance(plan_index, int) or not 0 <= plan_index < (1 << 28)):
             raise ValueError(f"plan_index must be an integer in [0, 2^28), got {plan_index!r}")
         m = self.model
+        index = self.passes if plan_index is None else plan_index
+        if self._mix_sig:       # before anything is allocated or launched
+            if index >= (1 << 26):
+                raise ValueError(f"audio_augment / mixup take pass indices below 2^26, got {index}")
+            if self._audio_aug and torch.is_tensor(batch_audios) and batch_audios.dim() == 3 and self.audio_augment["time_mask"] > batch_audios.shape[2]:
+                raise ValueError(f"audio_augment: time_mask = {self.audio_augment['time_mask']} is longer than the {batch_audios.shape[2]} "
+                                 "audio bins of this video")
         weights = self._check_weights(weights, batch_frames.shape[0] if torch.is_tensor(batch_frames) else 0)
         m._require_device()
         if not torch.is_tensor(batch_frames) or batch_frames.dim() != 4 or batch_frames.shape[1] != 3:
@@ -385,10 +428,11 @@ class VideoTrainer:
         if m._state is None:
             m._make_state()
         m._state[2:4].zero_()                       # subbatch_offset, iterations (main.py:173-175)
-        index = self.passes if plan_index is None else plan_index
         self.passes = index + 1
         if self._planned:
             ops.epoch_plan(self._plan, n_frames, self.seed, index, self.shuffle, **self.augment)
+        if self._mix_sig:
+            ops.epoch_plan2(self._plan2, self._plan, n_frames, self.seed, index, 30, max(bins, 1), **self.audio_augment, **self.mixup)
         if m.precision == "fp16":
             # the previous video's results have been read back by now (main.py:203): a cheap place to notice skipped steps and
             # halve the loss scale (AVM.update_loss_scale) — a static scale would otherwise stall training silently

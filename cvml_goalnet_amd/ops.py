@@ -1293,6 +1293,108 @@ def rows_copy_indexed(segments, plan):
     check(lib().goalnet_rows_copy_indexed(arr, len(segments), plan.data_ptr(), plan.shape[0], _s()), "rows_copy_indexed")
 
 
+# ---- audio augmentation and mixup on such a pass (include/goalnet_mix.h, csrc/mix.hip) -------------------------
+AUDIO_COEFFS = 30         # MFCC coefficients per frame: rows of the (N, 30, B) audio tables
+
+
+def _int_option(name, v, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0 or (hi is not None and v > hi):
+        raise ValueError(f"{name} must be an integer " + (">= 0" if hi is None else f"in [0, {hi}]") + f", got {v!r}")
+    return v
+
+
+def _f32_option(name, v, ok):
+    try:
+        f = ctypes.c_float(float(v)).value
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number, got {v!r}") from None
+    if isinstance(v, bool) or not ok(f):                # NaN fails every comparison
+        raise ValueError(f"{name} = {v!r} is outside its range")
+    return f
+
+
+def audio_augment_spec(max_shift=0, time_mask=0, coeff_mask=0, gain=0.0, noise=0.0):
+    """(max_shift, time_mask, coeff_mask, gain, noise) as goalnet_epoch_plan2 takes them — ValueError on a value outside its range,
+    before any launch and without a GPU. The two floats are rounded to fp32 here: that is what the draws are defined on.
+    (time_mask <= bins can only be checked against a video: goalnet_epoch_plan2's wrapper and train_video do that.)"""
+    return (_int_option("max_shift", max_shift, _lib.MAX_SHIFT), _int_option("time_mask", time_mask, None),
+            _int_option("coeff_mask", coeff_mask, AUDIO_COEFFS - 1), _f32_option("gain", gain, lambda f: 0.0 <= f < 1.0),
+            _f32_option("noise", noise, lambda f: 0.0 <= f < float("inf")))
+
+
+def mixup_spec(strength=0.0, p=0.0):
+    """(strength, p) as goalnet_epoch_plan2 takes them, rounded to fp32 — ValueError outside [0, 1], without a GPU"""
+    return _f32_option("strength", strength, lambda f: 0.0 <= f <= 1.0), _f32_option("p", p, lambda f: 0.0 <= f <= 1.0)
+
+
+def _plan2_ok(plan2, plan, who):
+    _plan_ok(plan, who)
+    _req(torch.is_tensor(plan2) and plan2.is_cuda and plan2.dtype == I32 and plan2.dim() == 2 and plan2.shape[1] == _lib.PLAN2_WORDS
+         and plan2.is_contiguous() and plan2.shape[0] >= plan.shape[0] and plan2.device == plan.device,
+         f"{who}: plan2 must be a contiguous int32 (>= {plan.shape[0]}, {_lib.PLAN2_WORDS}) GPU tensor beside the plan")
+
+
+def epoch_plan2(plan2, plan, n, seed, index, C, B, max_shift=0, time_mask=0, coeff_mask=0, gain=0.0, noise=0.0, strength=0.0, p=0.0):
+    """rows [0, n) of `plan2` (int32 (>= n, 12)) = the audio / mixup draws of pass `index` for the frames rows [0, n) of the finished
+    `plan` name: {a_shift, t0, tw, c0, cw, gain, partner, lambda, nkey lo, nkey hi, 0, 0}; the audio table is (rows, C, B)"""
+    max_shift, time_mask, coeff_mask, gain, noise = audio_augment_spec(max_shift, time_mask, coeff_mask, gain, noise)
+    strength, p = mixup_spec(strength, p)
+    if not 1 <= n <= _lib.EPOCH_MAX_N:
+        raise ValueError(f"a pass takes 1..{_lib.EPOCH_MAX_N} frames, got {n}")
+    if not 0 <= index < _lib.PLAN2_MAX_INDEX:
+        raise ValueError(f"pass index must be in [0, 2^26), got {index}")
+    if C < 1 or B < 1 or time_mask > B or coeff_mask > C - 1:
+        raise ValueError(f"time_mask = {time_mask} / coeff_mask = {coeff_mask} do not fit a ({C}, {B}) audio row")
+    _plan2_ok(plan2, plan, "epoch_plan2")
+    _req(plan.shape[0] >= n, "epoch_plan2: the plan tables are shorter than the pass")
+    check(lib().goalnet_epoch_plan2(plan2.data_ptr(), plan.data_ptr(), n, int(seed) & 0xFFFFFFFFFFFFFFFF, index, C, B, max_shift, time_mask,
+                                    coeff_mask, gain, noise, strength, p, _s()), "epoch_plan2")
+    return plan2
+
+
+def audio_gather_aug(table, out, plan, plan2, nrows, cursor, cursor_bias=0, gain=False, noise=0.0, mix=False):
+    """out[i] = the audio row plan[cursor + cursor_bias + i] names, shifted in time (edge-replicate), with `gain` scaled, with
+    `noise` > 0 plus uniform noise of that amplitude, time / coefficient masked (never coefficient 0) and, with `mix`, mixed with
+    its partner's as plan2 says; table (rows, C, B), out (nrows, C, B), fp32. No flag: values are moved as words. One launch."""
+    _chk(table, out)
+    _plan2_ok(plan2, plan, "audio_gather_aug")
+    _req(table.dtype == F32 and out.dtype == F32 and table.dim() == 3 and table.is_contiguous() and out.is_contiguous()
+         and tuple(out.shape) == (nrows,) + tuple(table.shape[1:]), "audio_gather_aug: fp32 (rows, C, B) table and (nrows, C, B) block")
+    noise = _f32_option("noise", noise, lambda f: 0.0 <= f < float("inf"))
+    flags = (_lib.AUDIO_GAIN if gain else 0) | (_lib.AUDIO_NOISE if noise > 0 else 0) | (_lib.AUDIO_MIX if mix else 0)
+    _, C, B = table.shape
+    check(lib().goalnet_audio_gather_aug(table.data_ptr(), table.shape[0], out.data_ptr(), plan.data_ptr(), plan2.data_ptr(), plan.shape[0], C, B,
+                                         nrows, _ctr(cursor), int(cursor_bias), flags, noise, _s()), "audio_gather_aug")
+    return out
+
+
+def frames_gather_mix(table, out, plan, plan2, nrows, cursor, cursor_bias=0, colour=False):
+    """frames_gather_aug with the mix: a row plan2 marks as mixed is lambda * its own augmented frame + (1 - lambda) * its partner's"""
+    _chk(table, out)
+    _plan2_ok(plan2, plan, "frames_gather_mix")
+    _req(table.dtype == F32 and out.dtype == F32 and table.dim() == 4 and table.is_contiguous() and out.is_contiguous()
+         and tuple(out.shape) == (nrows,) + tuple(table.shape[1:]), "frames_gather_mix: fp32 (rows, C, H, W) table and (nrows, C, H, W) block")
+    _, C, H, W = table.shape
+    check(lib().goalnet_frames_gather_mix(table.data_ptr(), table.shape[0], out.data_ptr(), plan.data_ptr(), plan2.data_ptr(), plan.shape[0], C, H,
+                                          W, nrows, _ctr(cursor), int(cursor_bias), 1 if colour else 0, _s()), "frames_gather_mix")
+    return out
+
+
+def rows_mix_indexed(segments, plan, plan2):
+    """fp32 row tables through the plan with the mix: segments of (table, block, nrows, cursor, cursor_bias);
+    block[i] = mix(table[plan[c + i].src], table[plan[partner].src]). One launch for up to 4 segments."""
+    _plan2_ok(plan2, plan, "rows_mix_indexed")
+    _req(1 <= len(segments) <= _lib.ROWCOPY_MAX, f"rows_mix_indexed: 1..{_lib.ROWCOPY_MAX} segments")
+    arr = (_lib.RowMix * len(segments))()
+    for k, (table, block, nrows, cursor, bias) in enumerate(segments):
+        _chk(table, block)
+        _req(table.is_contiguous() and block.is_contiguous() and table.dtype == F32 and block.dtype == F32, "rows_mix_indexed: contiguous fp32 tensors")
+        row_elems = table[0].numel() if table.dim() > 1 else 1
+        _req(block.numel() == row_elems * nrows, "rows_mix_indexed: block size")
+        arr[k] = _lib.RowMix(table.data_ptr(), block.data_ptr(), row_elems, nrows, _ctr(cursor), int(bias), table.shape[0])
+    check(lib().goalnet_rows_mix_indexed(arr, len(segments), plan.data_ptr(), plan2.data_ptr(), plan.shape[0], _s()), "rows_mix_indexed")
+
+
 # ---- inference mode around the model (csrc/summary.hip) ---------------------------------------------------------------------
 def frames_preprocess_strided(frames, stride, out, minmax):
     """out (n, 3, H, W) fp32 = frames_preprocess of frames[::stride], n = ceil(n_total / stride), read in place from the whole

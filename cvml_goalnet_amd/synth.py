@@ -85,6 +85,7 @@ TID_DROP = 4096  # + 8*step + layer: visbl.drop5, fusion.2, fusion.5, fusion.8, 
 TID_PARAM = 64  # 64 + index into PARAM_ORDER
 TID_GRADOUT = 40
 TID_PLAN = 1 << 30  # + 8*pass + option: order, flip, dx, dy, gain, bias of a shuffled / augmented pass (augment.py); far above TID_DROP's
+TID_PLAN2 = 3 << 30  # + 16*pass + option: the audio and mixup draws of such a pass (augment.py); above every TID_PLAN + 8*pass + option; pass < 2^26
 
 # torch-native state_dict parameter order (probed from the reference instance)
 PARAM_ORDER = [

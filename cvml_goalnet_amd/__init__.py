@@ -6,6 +6,7 @@ surface. See DESIGN.md / INTEGRATION.md.
     from cvml_goalnet_amd import VideoSummarizer   # /root/reference/main.py:315-345 (`--infer`) on a video resident on the GPU
     from cvml_goalnet_amd import epoch_plan, gather_augmented  # shuffled / augmented passes drawn on the GPU (extension)
     from cvml_goalnet_amd import epoch_plan2, gather_audio_augmented, gather_mixed, mix_rows  # audio augmentation and mixup on such a pass (extension)
+    from cvml_goalnet_amd import load_audio, to_mono, read_wav, resample_plan, resample_taps  # the audio front end: downmix and resample to 22 050 Hz on the GPU (extension)
     from cvml_goalnet_amd import EmaOptions        # a weight average behind the fused step; exact save / resume (extension)
     from cvml_goalnet_amd import TemporalSegmenter # KTS change points for a video outside the dataset (extension, parity unpinned)
 """
@@ -20,6 +21,7 @@ from .segment import Segmentation, TemporalSegmenter  # noqa: F401
 from .rankcorr import HumanConsistency, RankCorrelation, RankEvaluator, rank_correlation  # noqa: F401
 from .augment import epoch_plan, gather_augmented  # noqa: F401
 from .augment import epoch_plan2, gather_audio_augmented, gather_mixed, mix_rows  # noqa: F401
+from .waveform import load_audio, read_wav, resample_plan, resample_taps, to_mono  # noqa: F401
 
-__all__ = ["epoch_plan", "gather_augmented", "epoch_plan2", "gather_audio_augmented", "gather_mixed", "mix_rows", "AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "OptimOptions", "ParamGroup", "EmaOptions","VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
+__all__ = ["load_audio", "read_wav", "resample_plan", "resample_taps", "to_mono", "epoch_plan", "gather_augmented", "epoch_plan2", "gather_audio_augmented", "gather_mixed", "mix_rows", "AVM", "GoalnetError", "synth", "LIB_PATH", "optim", "OptimOptions", "ParamGroup", "EmaOptions","VideoSummarizer", "VideoSummary", "groundtruth", "TemporalSegmenter",
            "Segmentation", "RankEvaluator", "RankCorrelation", "HumanConsistency", "rank_correlation"]

@@ -278,6 +278,18 @@ PLAN2_WORDS = 12          # GOALNET_PLAN2_WORDS
 PLAN2_MAX_INDEX = 1 << 26  # GOALNET_PLAN2_MAX_INDEX
 AUDIO_GAIN, AUDIO_NOISE, AUDIO_MIX = 1, 2, 4      # GOALNET_AUDIO_*
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_wave.h, the ninth public header (the audio
+# front end: downmix and polyphase resampling to the feature rate): additions, the tables above stay as they are
+WAVE_PROTOTYPES = {
+    "goalnet_wave_plan": (c_int, [c_int, c_int, c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int64)]),
+    "goalnet_wave_resample": (c_int, [P, c_int, c_int64, c_int, P, c_int, c_int, c_int, c_int, P, c_int64, P]),
+}
+WAVE_F32, WAVE_S16 = 0, 1         # GOALNET_WAVE_F32 / _S16
+WAVE_MAX_RATIO = 16               # GOALNET_WAVE_MAX_RATIO
+WAVE_MAX_CHANNELS = 8             # GOALNET_WAVE_MAX_CHANNELS
+WAVE_MAX_RATE = 1 << 24           # GOALNET_WAVE_MAX_RATE
+
 _lib = None
 
 
@@ -296,7 +308,8 @@ def load():
             "There is no CPU / eager fallback for the AVM hot path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
-                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items(), *MIX_PROTOTYPES.items()):
+                              *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items(), *MIX_PROTOTYPES.items(),
+                              *WAVE_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

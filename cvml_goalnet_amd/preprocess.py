@@ -5,9 +5,12 @@ reference's I/O). Output is the `(N, 3, H, W)` float32 tensor `AVM` takes, left 
 
 PARITY UNPINNED: OpenCV is not in the build image; kernel and oracle (oracle/preproc_ref.py) restate its documented
 INTER_LINEAR algorithm and agree with each other bit for bit, but neither has been compared with cv2 itself.
-The MFCC half of the reference's pre-processing (utils.py:313-349) is not built (librosa absent).
+The audio half (utils.py:313-349) is `extract_audio_features` below, from the waveform on; `waveform.py` makes that waveform from
+decoded samples or a 16-bit PCM WAV file (downmix and resampling on the device, scipy's arithmetic; parity with librosa unpinned).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -143,13 +146,18 @@ def slot_bounds(n_samples: int, n_frames: int):
 
 
 def extract_audio_features(y, n_frames: int, bin_length: int, sr: int = SR, device=None) -> torch.Tensor:
-    """`utils.extract_audio_features(audio_fp, n_frames, bin_length)` (utils.py:313-349) from the decoded waveform on:
-    `y` is what `librosa.load(audio_fp)` returns (mono float32 at `sr` = 22 050 Hz; decoding and resampling the file stay
-    the reference's I/O). Returns the (n_frames, 30, bin_length) float32 tensor AudBl takes, on the GPU.
+    """`utils.extract_audio_features(audio_fp, n_frames, bin_length)` (utils.py:313-349). `y` is either the file itself — a
+    `str` / `os.PathLike` naming a 16-bit PCM WAV, which `waveform.load_audio` reads, averages to mono and resamples to `sr` on
+    the device (the reference's own call; scipy's resampling arithmetic, not librosa's soxr_hq: parity unpinned) — or what
+    `librosa.load(audio_fp)` returns: the mono float32 waveform at `sr` = 22 050 Hz, taken as it is.
+    Returns the (n_frames, 30, bin_length) float32 tensor AudBl takes, on the GPU.
     PARITY UNPINNED for the MFCC values (librosa is not installed in the build image); the resample is pinned against scipy."""
     if not torch.cuda.is_available():
         raise GoalnetError("audio pre-processing runs on the GPU (torch.cuda.is_available() is False); there is no CPU fallback")
     dev = torch.device(device if device is not None else "cuda:0")
+    if isinstance(y, (str, os.PathLike)):
+        from .waveform import load_audio               # waveform.py imports this module
+        y, sr = load_audio(y, sr, dev)
     wav = (y if torch.is_tensor(y) else torch.from_numpy(np.ascontiguousarray(y))).to(device=dev, dtype=torch.float32).contiguous().view(-1)
     if n_frames < 1 or wav.numel() < 1:
         raise ValueError("no audio / no frames")

@@ -24,6 +24,7 @@ import torch
 
 from .postprocess import SummaryEvaluator
 from .preprocess import SR, extract_audio_features, frames_to_tensor
+from .waveform import load_audio, to_mono
 
 
 @dataclass
@@ -79,11 +80,16 @@ class VideoSummarizer:
             ev = self._evaluators[full_n] = SummaryEvaluator(self.change_points, full_n, self.skip_frames, None, self.model._device)
         return ev
 
-    def __call__(self, full_frames, audio_features=None, waveform=None, sr: int = SR, bin_length=None) -> VideoSummary:
+    def __call__(self, full_frames, audio_features=None, waveform=None, sr: int = SR, bin_length=None, audio_fp=None,
+                 target_sr=None) -> VideoSummary:
         """full_frames: (full_n, H0, W0, 3) uint8, the decoded video (`get_frame_tensor`, utils.py:294-305), on the GPU or the host.
         With `audio_included=True` give either audio_features (N, 30, B) for the N = ceil(full_n / skip_frames) sampled frames, or
         the decoded `waveform` at `sr` together with `bin_length` (the reference's own call at main.py:321 omits bin_length and
-        cannot run, so nothing is guessed)."""
+        cannot run, so nothing is guessed), or `audio_fp`, the 16-bit PCM WAV of the sound track, with `bin_length`.
+        target_sr=None: the waveform is taken as mono at `sr` and the features are computed at that rate, as before. With
+        target_sr (22 050 for a model trained on the reference's features) the waveform — (n,) or (n, channels), float32 or
+        int16 at `sr` — first goes through `waveform.to_mono` on the device and the features are computed at target_sr.
+        `audio_fp` always does (target_sr=None means 22 050 there). No synchronisation is added."""
         model = self.model
         t = full_frames if torch.is_tensor(full_frames) else torch.from_numpy(np.ascontiguousarray(full_frames))
         if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
@@ -91,8 +97,10 @@ class VideoSummarizer:
         full_n = int(t.shape[0])
         n = (full_n + self.skip_frames - 1) // self.skip_frames
         if model.audio_included:
-            if audio_features is None and waveform is None:
-                raise ValueError("audio_included=True needs audio_features or a waveform")
+            if audio_features is None and waveform is None and audio_fp is None:
+                raise ValueError("audio_included=True needs audio_features or a waveform (decoded, or audio_fp naming its WAV file)")
+            if waveform is not None and audio_fp is not None:
+                raise ValueError("give a waveform or audio_fp, not both")
             if audio_features is None and bin_length is None:
                 raise ValueError("a waveform needs bin_length (utils.extract_audio_features(audio_fp, n_frames, bin_length))")
             if audio_features is not None:
@@ -108,6 +116,11 @@ class VideoSummarizer:
             if model.audio_included:
                 if audio_features is not None:
                     audio = audio_features.detach().to(device=dev, dtype=torch.float32).contiguous()
+                elif audio_fp is not None:
+                    wav, rate = load_audio(audio_fp, SR if target_sr is None else int(target_sr), dev)
+                    audio = extract_audio_features(wav, n, int(bin_length), rate, dev)
+                elif target_sr is not None:
+                    audio = extract_audio_features(to_mono(waveform, sr, int(target_sr), dev), n, int(bin_length), int(target_sr), dev)
                 else:
                     audio = extract_audio_features(waveform, n, int(bin_length), sr, dev)
             out, _ = model.forward_device(audio, visual, save=False)

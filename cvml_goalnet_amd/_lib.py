@@ -290,6 +290,19 @@ WAVE_MAX_RATIO = 16               # GOALNET_WAVE_MAX_RATIO
 WAVE_MAX_CHANNELS = 8             # GOALNET_WAVE_MAX_CHANNELS
 WAVE_MAX_RATE = 1 << 24           # GOALNET_WAVE_MAX_RATE
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_nv12.h, the tenth public header (NV12 frames
+# in: conversion, strided pre-processing and clip gather): additions, the tables above stay as they are. `coeffs`
+# is a HOST int32[8] table (checked before any launch), so it travels as a ctypes pointer, not as a device address
+NV12_PROTOTYPES = {
+    "goalnet_nv12_to_bgr": (c_int, [P, c_int, c_int, c_int, c_int64, c_int64, c_int64, ctypes.POINTER(c_int32), P, P]),
+    "goalnet_nv12_preprocess_strided": (c_int, [P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, ctypes.POINTER(c_int32), P, c_int,
+                                                c_int, P, P]),
+    "goalnet_nv12_gather_clips_bgr_ws_bytes": (c_size_t, [c_int]),
+    "goalnet_nv12_gather_clips_bgr": (c_int, [P, c_int, c_int, c_int, c_int64, c_int64, c_int64, ctypes.POINTER(c_int32), P, P, c_int, P,
+                                              c_int64, P, P, P, P, c_size_t, P]),
+}
+NV12_MIN_SHIFT, NV12_MAX_SHIFT = 8, 24        # GOALNET_NV12_MIN_SHIFT / _MAX_SHIFT
+
 _lib = None
 
 
@@ -309,7 +322,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
                               *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items(), *MIX_PROTOTYPES.items(),
-                              *WAVE_PROTOTYPES.items()):
+                              *WAVE_PROTOTYPES.items(), *NV12_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

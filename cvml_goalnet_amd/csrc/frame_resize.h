@@ -1,7 +1,8 @@
 // One output pixel of the loader's frame pre-processing (/root/reference/utils.py:284-285): min-max normalisation in float64,
 // float32, then OpenCV's INTER_LINEAR resize for float32 images (imgproc/resize.cpp: half-pixel centres, floor, border clamp,
 // horizontal pass then vertical pass). Shared by goalnet_frames_preprocess (preproc.hip) and goalnet_frames_preprocess_strided
-// (summary.hip) so that both compile the same arithmetic: their outputs are bit-identical by construction.
+// (summary.hip), and through frame_resize_pixel_of by goalnet_nv12_preprocess_strided (nv12.hip), so that all compile the same
+// arithmetic: their outputs are bit-identical by construction.
 #pragma once
 #include "common.h"
 
@@ -10,9 +11,11 @@ namespace goalnet {
 // rounded product / sum without fma contraction (OpenCV's scalar path multiplies and adds separately)
 __device__ __forceinline__ float mul_rn(float a, float b) { return __builtin_fmaf(a, b, 0.0f); }
 
-// f: the source frame [H0][W0][3] uint8; mn / mx: its min and max over all three channels; (c, dy, dx): the output element
-__device__ __forceinline__ float frame_resize_pixel(const uint8_t* __restrict__ f, int mn, int mx, int c, int dy, int dx, int H0, int W0,
-                                                    double scale_x, double scale_y) {
+// fetch(yy, xx): the 0 .. 255 value of source pixel (yy, xx) in the output element's channel (packed BGR below; nv12.hip converts
+// the pixel on the way); mn / mx: the frame's min and max over all three channels; (dy, dx): the output element
+template <typename Fetch>
+__device__ __forceinline__ float frame_resize_pixel_of(Fetch fetch, int mn, int mx, int dy, int dx, int H0, int W0, double scale_x,
+                                                       double scale_y) {
     // source coordinates, resize.cpp: fx = (float)((dx + 0.5) * scale_x - 0.5); sx = floor(fx); fx -= sx; border clamp
     float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
     int sx = (int)floorf(fx);
@@ -26,11 +29,18 @@ __device__ __forceinline__ float frame_resize_pixel(const uint8_t* __restrict__ 
     if (sy >= H0 - 1) { sy = H0 - 1; fy = 0.f; }
     const int sx1 = sx + 1 < W0 ? sx + 1 : W0 - 1, sy1 = sy + 1 < H0 ? sy + 1 : H0 - 1;
     const double den = (double)(mx - mn) + 1e-7;                        // uint8 difference, then + 1e-7 in float64
-    auto px = [&](int yy, int xx) -> float { return (float)((double)(f[((int64_t)yy * W0 + xx) * 3 + c] - mn) / den); };
+    auto px = [&](int yy, int xx) -> float { return (float)((double)(fetch(yy, xx) - mn) / den); };
     const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
     const float h0 = mul_rn(px(sy, sx), a0) + mul_rn(px(sy, sx1), a1);   // horizontal pass on the two source rows
     const float h1 = mul_rn(px(sy1, sx), a0) + mul_rn(px(sy1, sx1), a1);
     return mul_rn(h0, b0) + mul_rn(h1, b1);                             // vertical pass
+}
+
+// f: the source frame [H0][W0][3] uint8; c: the output element's channel
+__device__ __forceinline__ float frame_resize_pixel(const uint8_t* __restrict__ f, int mn, int mx, int c, int dy, int dx, int H0, int W0,
+                                                    double scale_x, double scale_y) {
+    return frame_resize_pixel_of([&](int yy, int xx) -> int { return f[((int64_t)yy * W0 + xx) * 3 + c]; }, mn, mx, dy, dx, H0, W0, scale_x,
+                                 scale_y);
 }
 
 // out[N][3][H][W] from frames n * frame_pitch (bytes) of `frames`; minmax[n] = {min, max} of that frame

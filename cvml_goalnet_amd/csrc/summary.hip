@@ -6,6 +6,7 @@
 // summary mask of utils.py:639-641 (postproc.hip) is end-INCLUSIVE [a, b]: the mask has one frame more per selected clip.
 #include "common.h"
 #include "frame_resize.h"
+#include "clip_scan.h"
 
 using namespace goalnet;
 
@@ -70,52 +71,6 @@ __global__ __launch_bounds__(256) void frame_resize_strided_kernel(const uint8_t
 }
 
 // ---- clip gather ----------------------------------------------------------------------------------------------------------
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-size_t offsets_bytes(int n_clips) { return align256((size_t)(n_clips + 1) * sizeof(int64_t)); }
-
-// One block. offsets[c] = number of summary frames in front of clip c (exclusive scan of the selected clips' slice lengths),
-// offsets[n_clips] = their total; starts[c] = first source frame of clip c. [a:b) clamped like a Python slice (as clip_info_kernel).
-__global__ __launch_bounds__(256) void clip_offsets_kernel(const int32_t* __restrict__ cps, const int32_t* __restrict__ selected, int n_clips,
-                                                          int full_n, int64_t capacity, int64_t* __restrict__ offsets,
-                                                          int32_t* __restrict__ starts, int64_t* __restrict__ count, int32_t* __restrict__ status) {
-    __shared__ int64_t s[256];
-    const int t = threadIdx.x;
-    const int per = (n_clips + 255) / 256;
-    const int lo = t * per < n_clips ? t * per : n_clips, hi = lo + per < n_clips ? lo + per : n_clips;
-    auto slice = [&](int c, int& a) -> int {
-        a = cps[2 * c];
-        int b = cps[2 * c + 1];
-        if (a < 0) a = a + full_n < 0 ? 0 : a + full_n;
-        if (b < 0) b = b + full_n < 0 ? 0 : b + full_n;
-        a = a > full_n ? full_n : a;
-        b = b > full_n ? full_n : b;
-        return (selected[c] != 0 && b > a) ? b - a : 0;
-    };
-    int64_t local = 0;
-    for (int c = lo; c < hi; ++c) { int a; local += slice(c, a); }
-    s[t] = local;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int64_t v = t >= o ? s[t - o] : 0;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-    int64_t run = s[t] - local;
-    for (int c = lo; c < hi; ++c) {
-        int a;
-        const int len = slice(c, a);
-        offsets[c] = run;
-        starts[c] = a;
-        run += len;
-    }
-    if (t == 255) {
-        offsets[n_clips] = s[255];
-        *count = s[255];
-        *status = s[255] > capacity ? 1 : 0;
-    }
-}
-
 // Summary frame k = source frame starts[c] + (k - offsets[c]) of the clip c with offsets[c] <= k < offsets[c + 1]. A block copies one
 // tile (256 lanes x 4 x sizeof(V) bytes of one frame) per iteration and strides over the tiles of the first min(total, capacity)
 // frames; the total is read from the scan's output, so the grid is sized from the capacity without a host round trip.

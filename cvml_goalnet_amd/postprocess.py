@@ -27,7 +27,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, nv12, ops
 from ._lib import GoalnetError, check
 from .ops import _s
 
@@ -253,7 +253,7 @@ class SummaryEvaluator:
         self._status(self.result.cpu())
         return torch.nonzero(self.selected).flatten().tolist(), self.mask.cpu().numpy()
 
-    def summarize(self, batch_importances, full_frames):
+    def summarize(self, batch_importances, full_frames, nv12_layout=None):
         """utils.py:606-643 with `full_frames` given, the call of main.py:336-345. full_frames: (full_n_frames, H0, W0, C) uint8, on
         the GPU or the host (then uploaded). Returns, in the reference's order, (summarized_video, summarized_video_frame_indices):
         the frames of the selected clips `np.concatenate([full_frames[a:b] ...])` (utils.py:634, end-exclusive slices) as a uint8
@@ -262,20 +262,36 @@ class SummaryEvaluator:
         `last_selected` the selected clip indices. The summary is a view of a buffer of `capacity = int(0.15 * full_n_frames)`
         frames: the knapsack keeps sum(int(5 * len)) <= int(5 * capacity) and a clip's slice length is its knapsack weight when
         the video has full_n_frames frames, so the bound is exact. Postprocess and gather are launched back to back; one
-        read-back fetches status, count, selection and mask."""
+        read-back fetches status, count, selection and mask.
+        nv12_layout = (frame_size, uv_row, colorspace, output_format): full_frames is NV12, (full_n_frames, rows, pitch) uint8
+        (cvml_goalnet_amd/nv12.py). output_format "bgr" converts the selected frames on the way into a (count, H0, W0, 3) summary;
+        "nv12" copies them as they are, (count, rows, pitch)."""
         t = full_frames if torch.is_tensor(full_frames) else torch.from_numpy(np.ascontiguousarray(full_frames))
-        if t.dtype != U8 or t.dim() != 4:
+        bgr_shape = None
+        if nv12_layout is not None:
+            frame_size, uv_row, colorspace, output_format = nv12_layout
+            if output_format not in nv12.PIXEL_FORMATS:
+                raise ValueError(f"unknown output_format {output_format!r}: one of {', '.join(nv12.PIXEL_FORMATS)}")
+            t = nv12._frames(t)
+            h0, w0 = nv12.nv12_layout(t.shape, frame_size, uv_row)[:2]
+            if output_format == "bgr":
+                bgr_shape = (h0, w0, 3)
+        elif t.dtype != U8 or t.dim() != 4:
             raise ValueError("full_frames must be uint8 (full_n_frames, H0, W0, C)")
         if t.shape[0] != self.full_n:
             raise ValueError(f"full_frames holds {t.shape[0]} frames, the evaluator was built for {self.full_n}")
         t = t.to(self.device).contiguous()
         cap = self.capacity
-        out = torch.empty((max(cap, 1),) + tuple(t.shape[1:]), dtype=U8, device=self.device)
+        out = torch.empty((max(cap, 1),) + (tuple(t.shape[1:]) if bgr_shape is None else bgr_shape), dtype=U8, device=self.device)
         src_index = torch.empty(max(cap, 1), dtype=I32, device=self.device)
         base = self._packed.data_ptr()
         self._launch(batch_importances, with_fscore=False, status_ptr=base + 12)
         with torch.cuda.device(self.device):
-            ops.gather_clips(t, self.cps, self.selected, out, cap, src_index, self._packed[0:8].view(I64), self._packed[8:12].view(I32))
+            if bgr_shape is None:
+                ops.gather_clips(t, self.cps, self.selected, out, cap, src_index, self._packed[0:8].view(I64), self._packed[8:12].view(I32))
+            else:
+                nv12.gather_clips_bgr(t, frame_size, uv_row, colorspace, self.cps, self.selected, out, cap, src_index,
+                                      self._packed[0:8].view(I64), self._packed[8:12].view(I32))
         host = self._packed.cpu()                                       # the one synchronising read-back
         count = int(host[0:8].view(I64)[0])
         gstatus, pstatus = host[8:16].view(I32).tolist()

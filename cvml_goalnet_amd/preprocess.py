@@ -15,18 +15,26 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, nv12, ops
 from ._lib import GoalnetError, check
 from .ops import _s
 
 
-def frames_to_tensor(frames, size=(40, 40), device=None, stride: int = 1) -> torch.Tensor:
+def frames_to_tensor(frames, size=(40, 40), device=None, stride: int = 1, pixel_format: str = "bgr", frame_size=None, uv_row=None,
+                     colorspace="bt601") -> torch.Tensor:
     """frames: (N, H0, W0, 3) uint8 (numpy or torch, BGR as cv2 decodes); size = (width, height) as `cv2.resize` takes it.
     Returns the (N, 3, height, width) float32 GPU tensor of utils.py:291.
     stride > 1: `frames` is the whole decoded video and every stride-th frame is kept (`count % skip_frames == 0`,
     utils.py:283): the ceil(N / stride) frames 0, stride, 2 stride, ... are read in place from a video that is resident on the
     GPU (no `frames[::stride].contiguous()` copy; csrc/summary.hip), bit-identical to the stride-1 call on that copy. A host
-    array is sliced before the upload instead."""
+    array is sliced before the upload instead.
+    pixel_format="nv12": `frames` is (N, rows, pitch) uint8 NV12 with `frame_size` = (H0, W0), the chroma plane at row `uv_row`
+    (default H0) and the colour table `colorspace` (cvml_goalnet_amd/nv12.py). Only the pixels the resize reads are converted, in
+    registers; the result is bit-identical to this function on `nv12_to_bgr(frames, ...)`, for every stride."""
+    if pixel_format not in nv12.PIXEL_FORMATS:
+        raise ValueError(f"unknown pixel_format {pixel_format!r}: one of {', '.join(nv12.PIXEL_FORMATS)}")
+    if pixel_format == "nv12":
+        return _nv12_to_tensor(frames, size, device, stride, frame_size, uv_row, colorspace)
     if not torch.cuda.is_available():
         raise GoalnetError("frame pre-processing runs on the GPU (torch.cuda.is_available() is False); there is no CPU fallback")
     dev = torch.device(device if device is not None else "cuda:0")
@@ -55,6 +63,21 @@ def frames_to_tensor(frames, size=(40, 40), device=None, stride: int = 1) -> tor
         check(_lib.load().goalnet_frames_preprocess(t.data_ptr(), n, h0, w0, out.data_ptr(), h, w, scratch.data_ptr(), _s()),
               "frames_preprocess")
     return out
+
+
+def _nv12_to_tensor(frames, size, device, stride, frame_size, uv_row, colorspace) -> torch.Tensor:
+    t = nv12._frames(frames)
+    nv12.nv12_layout(t.shape, frame_size, uv_row)                       # a wrong layout is refused before anything is uploaded
+    nv12._table(colorspace)                                             # and an unknown colour space
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    if t.shape[0] < 1:
+        raise ValueError("no frames")
+    dev = nv12._device(device)
+    if stride > 1 and not t.is_cuda:
+        t, stride = t[::stride], 1                                      # upload the kept frames only
+    return nv12.preprocess_strided(t.to(dev).contiguous(), stride, size, frame_size, uv_row, colorspace)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from . import nv12
 from .postprocess import SummaryEvaluator
 from .preprocess import SR, extract_audio_features, frames_to_tensor
 from .waveform import load_audio, to_mono
@@ -29,7 +30,8 @@ from .waveform import load_audio, to_mono
 
 @dataclass
 class VideoSummary:
-    frames: torch.Tensor           # (count, H0, W0, C) uint8 on the device: the summarised video (utils.py:634)
+    frames: torch.Tensor           # (count, H0, W0, C) uint8 on the device: the summarised video (utils.py:634); (count, rows, pitch)
+                                   # NV12 with output_format="nv12"
     frame_indices: np.ndarray      # (full_n,) uint8 mask: summarized_video_frame_indices (utils.py:637-641, end-inclusive)
     selected: List[int]            # indices of the selected clips (rows of change_points)
     src_index: torch.Tensor        # (count,) int32 on the device: the source frame of every summary frame
@@ -81,7 +83,8 @@ class VideoSummarizer:
         return ev
 
     def __call__(self, full_frames, audio_features=None, waveform=None, sr: int = SR, bin_length=None, audio_fp=None,
-                 target_sr=None) -> VideoSummary:
+                 target_sr=None, pixel_format: str = "bgr", frame_size=None, uv_row=None, colorspace="bt601",
+                 output_format: str = "bgr") -> VideoSummary:
         """full_frames: (full_n, H0, W0, 3) uint8, the decoded video (`get_frame_tensor`, utils.py:294-305), on the GPU or the host.
         With `audio_included=True` give either audio_features (N, 30, B) for the N = ceil(full_n / skip_frames) sampled frames, or
         the decoded `waveform` at `sr` together with `bin_length` (the reference's own call at main.py:321 omits bin_length and
@@ -89,10 +92,28 @@ class VideoSummarizer:
         target_sr=None: the waveform is taken as mono at `sr` and the features are computed at that rate, as before. With
         target_sr (22 050 for a model trained on the reference's features) the waveform — (n,) or (n, channels), float32 or
         int16 at `sr` — first goes through `waveform.to_mono` on the device and the features are computed at target_sr.
-        `audio_fp` always does (target_sr=None means 22 050 there). No synchronisation is added."""
+        `audio_fp` always does (target_sr=None means 22 050 there). No synchronisation is added.
+        pixel_format="nv12": full_frames is what a hardware decoder leaves, (full_n, rows, pitch) uint8 NV12 with `frame_size` =
+        (H0, W0), the chroma plane at row `uv_row` (default H0) and the colour table `colorspace` (cvml_goalnet_amd/nv12.py). The
+        sampled frames are converted inside the pre-processing and the selected clips inside the gather; no BGR copy of the video
+        is made. output_format="bgr" (the default) returns `frames` as (count, H0, W0, 3), what `export_video` takes;
+        output_format="nv12" returns the selected source frames as they are, (count, rows, pitch), for a hardware encoder."""
         model = self.model
         t = full_frames if torch.is_tensor(full_frames) else torch.from_numpy(np.ascontiguousarray(full_frames))
-        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+        if pixel_format not in nv12.PIXEL_FORMATS:
+            raise ValueError(f"unknown pixel_format {pixel_format!r}: one of {', '.join(nv12.PIXEL_FORMATS)}")
+        if output_format not in nv12.PIXEL_FORMATS:
+            raise ValueError(f"unknown output_format {output_format!r}: one of {', '.join(nv12.PIXEL_FORMATS)}")
+        layout = None
+        if pixel_format == "nv12":
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[0] < 1:
+                raise ValueError("NV12 full_frames must be uint8 (full_n, rows, pitch) with at least one frame")
+            nv12.nv12_layout(t.shape, frame_size, uv_row)
+            nv12._table(colorspace)
+            layout = (frame_size, uv_row, colorspace, output_format)
+        elif output_format != "bgr":
+            raise ValueError("output_format='nv12' needs pixel_format='nv12': BGR frames are not converted to NV12")
+        elif t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
             raise ValueError("full_frames must be uint8 (full_n, H0, W0, 3) with at least one frame")
         full_n = int(t.shape[0])
         n = (full_n + self.skip_frames - 1) // self.skip_frames
@@ -111,7 +132,11 @@ class VideoSummarizer:
         dev = model._device
         t = t.to(dev).contiguous()
         with torch.cuda.device(dev), torch.no_grad():
-            visual = frames_to_tensor(t, self.size, dev, stride=self.skip_frames)
+            if layout is None:
+                visual = frames_to_tensor(t, self.size, dev, stride=self.skip_frames)
+            else:
+                visual = frames_to_tensor(t, self.size, dev, stride=self.skip_frames, pixel_format="nv12", frame_size=frame_size,
+                                          uv_row=uv_row, colorspace=colorspace)
             audio = None
             if model.audio_included:
                 if audio_features is not None:
@@ -131,5 +156,5 @@ class VideoSummarizer:
             else:
                 cps = self.change_points
                 ev = self._evaluator(full_n)
-            frames, mask = ev.summarize(predictions, t)
+            frames, mask = ev.summarize(predictions, t) if layout is None else ev.summarize(predictions, t, nv12_layout=layout)
         return VideoSummary(frames, mask, ev.last_selected, ev.last_src_index, predictions, cps)

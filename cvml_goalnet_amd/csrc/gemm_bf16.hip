@@ -659,28 +659,23 @@ int goalnet_cast_f32(const void* x_bf16, float* y, int64_t n, int f16, void* str
     return 0;
 }
 
-int goalnet_bn_apply_bf16(const float* x, const float* scale, const float* shift, void* y_bf16, int64_t n, int C, int f16, void* stream) {
-    GN_REQUIRE(x && scale && shift && y_bf16, GOALNET_E_NULL, "bn_apply_bf16: null pointer");
-    GN_REQUIRE(n > 0 && C > 0 && C % 8 == 0 && n % C == 0, GOALNET_E_SHAPE, "bn_apply_bf16: n must be a multiple of C, C of 8");
-    GN_REQUIRE(aligned16(x) && aligned16(y_bf16) && aligned16(scale) && aligned16(shift), GOALNET_E_ALIGN, "bn_apply_bf16: alignment");
-    if (f16) hipLaunchKernelGGL((bn_apply_bf16_kernel<false, true>), dim3(grid1d(n / 8)), dim3(256), 0, (hipStream_t)stream, (const void*)x, scale, shift,
-                                (__hip_bfloat16*)y_bf16, n / 8, C);
-    else hipLaunchKernelGGL((bn_apply_bf16_kernel<false, false>), dim3(grid1d(n / 8)), dim3(256), 0, (hipStream_t)stream, (const void*)x, scale, shift,
-                            (__hip_bfloat16*)y_bf16, n / 8, C);
-    GN_LAUNCH_CHECK("bn_apply_bf16");
+// fp32 (h16 = false) or 16-bit (the _p16 entry point) input; `who` = the entry point's name in error texts
+static int bn_apply_h16(const char* who, bool h16, const void* x, const float* scale, const float* shift, void* y_bf16, int64_t n, int C, int f16,
+                        void* stream) {
+    GN_REQUIRE(x && scale && shift && y_bf16, GOALNET_E_NULL, "%s: null pointer", who);
+    GN_REQUIRE(n > 0 && C > 0 && C % 8 == 0 && n % C == 0, GOALNET_E_SHAPE, "%s: n must be a multiple of C, C of 8", who);
+    GN_REQUIRE(aligned16(x) && aligned16(y_bf16) && aligned16(scale) && aligned16(shift), GOALNET_E_ALIGN, "%s: alignment", who);
+    const auto kernel = !h16 ? (f16 ? bn_apply_bf16_kernel<false, true> : bn_apply_bf16_kernel<false, false>)
+                             : (f16 ? bn_apply_bf16_kernel<true, true> : bn_apply_bf16_kernel<true, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid1d(n / 8)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, (__hip_bfloat16*)y_bf16, n / 8, C);
+    GN_LAUNCH_CHECK(who);
     return 0;
 }
-
+int goalnet_bn_apply_bf16(const float* x, const float* scale, const float* shift, void* y_bf16, int64_t n, int C, int f16, void* stream) {
+    return bn_apply_h16("bn_apply_bf16", false, x, scale, shift, y_bf16, n, C, f16, stream);
+}
 int goalnet_bn_apply_bf16_p16(const void* x_bf16, const float* scale, const float* shift, void* y_bf16, int64_t n, int C, int f16, void* stream) {
-    GN_REQUIRE(x_bf16 && scale && shift && y_bf16, GOALNET_E_NULL, "bn_apply_bf16_p16: null pointer");
-    GN_REQUIRE(n > 0 && C > 0 && C % 8 == 0 && n % C == 0, GOALNET_E_SHAPE, "bn_apply_bf16_p16: n must be a multiple of C, C of 8");
-    GN_REQUIRE(aligned16(x_bf16) && aligned16(y_bf16) && aligned16(scale) && aligned16(shift), GOALNET_E_ALIGN, "bn_apply_bf16_p16: alignment");
-    if (f16) hipLaunchKernelGGL((bn_apply_bf16_kernel<true, true>), dim3(grid1d(n / 8)), dim3(256), 0, (hipStream_t)stream,
-                                x_bf16, scale, shift, (__hip_bfloat16*)y_bf16, n / 8, C);
-    else hipLaunchKernelGGL((bn_apply_bf16_kernel<true, false>), dim3(grid1d(n / 8)), dim3(256), 0, (hipStream_t)stream,
-                            x_bf16, scale, shift, (__hip_bfloat16*)y_bf16, n / 8, C);
-    GN_LAUNCH_CHECK("bn_apply_bf16_p16");
-    return 0;
+    return bn_apply_h16("bn_apply_bf16_p16", true, x_bf16, scale, shift, y_bf16, n, C, f16, stream);
 }
 
 int goalnet_conv3x3_fwd_bf16(const void* x_bf16, const void* w_bf16, const float* bias, int relu, float* y,
@@ -694,8 +689,7 @@ int goalnet_conv3x3_fwd_bf16(const void* x_bf16, const void* w_bf16, const float
     GN_REQUIRE(M < (1ll << 31) - 256, GOALNET_E_SHAPE, "conv3x3_fwd_bf16: N*H*W too large");
     ConvALoaderH::P ap{(const __hip_bfloat16*)x_bf16, H, W, Cin, M};
     KCLoaderH::P bp{(const __hip_bfloat16*)w_bf16, (int64_t)9 * Cin, Cout};
-    EpiP ep{EPI_BIAS_RELU, y, Cout, (int)M, Cout, bias, relu, nullptr, 0, nullptr, 0, 0};
-    return launch_gemm_h<ConvALoaderH, KCLoaderH>("conv3x3_fwd_bf16", ap, bp, ep, M, Cout, 9 * Cin / BKH, 1, 0, f16 != 0, (hipStream_t)stream);
+    return launch_gemm_h<ConvALoaderH, KCLoaderH>("conv3x3_fwd_bf16", ap, bp, epi_act(y, Cout, (int)M, Cout, bias, relu), M, Cout, 9 * Cin / BKH, 1, 0, f16 != 0, (hipStream_t)stream);
 }
 
 static int linear_splits_h(int M, int64_t K, int J) {
@@ -703,15 +697,19 @@ static int linear_splits_h(int M, int64_t K, int J) {
     return pick_splits(tiles, (int)(K / BKH));
 }
 
-// many rows and a long reduction (linear5 at the bench shape): the 256 x 256 phased kernel with XCD-local K-splits
-static bool linear_use_256(int M, int64_t K, int J) {
+// Tile choice of every 16-bit contraction: the 256 x 256 phased tile (gemm_bf16_256.hip) where the shape rule `by_shape` of the role
+// says so; GOALNET_BF16_TILE=128 / 256 forces a choice (tests, A/B runs). Read at every call: tests flip it inside one process.
+static bool use_256(bool by_shape) {
     const char* forced = getenv("GOALNET_BF16_TILE");
-    return forced ? forced[0] == '2' : (M >= 512 && J >= 256 && K >= (1ll << 18));
+    return forced ? forced[0] == '2' : by_shape;
 }
+
+// many rows and a long reduction (linear5 at the bench shape): the 256 x 256 phased kernel with XCD-local K-splits
+static bool linear_use_256(int M, int64_t K, int J) { return use_256(M >= 512 && J >= 256 && K >= (1ll << 18)); }
 
 size_t goalnet_linear_fwd_bf16_ws_bytes(int M, int64_t K, int J) {
     if (M <= 0 || K <= 0 || J <= 0) return 0;
-    const int a = linear_splits_h(M, K, J), b = linear_fwd_splits_256(M, K, J);     // enough for either kernel
+    const int a = linear_splits_h(M, K, J), b = linear_fwd_splits_256(1, M, K, J);  // enough for either kernel
     const int s = a > b ? a : b;
     return s > 1 ? (size_t)s * (size_t)M * (size_t)J * sizeof(float) : 0;
 }
@@ -725,27 +723,26 @@ int goalnet_linear_fwd_bf16(const void* x_bf16, int64_t ldx, const void* w_bf16,
     GN_REQUIRE(ldx % 8 == 0 && ldy % 4 == 0, GOALNET_E_ALIGN, "linear_fwd_bf16: leading dimensions must be multiples of 16 bytes (ldx %% 8, ldy %% 4)");
     GN_REQUIRE(aligned16(x_bf16) && aligned16(w_bf16) && aligned16(y), GOALNET_E_ALIGN, "linear_fwd_bf16: alignment");
     hipStream_t st = (hipStream_t)stream;
+    const EpiP efinal = epi_act(y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult);
     if (linear_use_256(M, K, J)) {
-        const int ns = linear_fwd_splits_256(M, K, J);
+        const int ns = linear_fwd_splits_256(1, M, K, J);
         if (ns > 1) {
             GN_REQUIRE(ws && aligned16(ws) && ws_bytes >= (size_t)ns * (size_t)M * (size_t)J * sizeof(float), GOALNET_E_WORKSPACE,
                        "linear_fwd_bf16: workspace too small");
-            const EpiP efin{(dropmask || mult_out) ? EPI_FULL : EPI_BIAS_RELU, y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult, 0};
-            const int rc2 = launch_linear_fwd_bf16_256("linear_fwd_bf16(256)", (const __hip_bfloat16*)x_bf16, ldx, (const __hip_bfloat16*)w_bf16,
-                                                       M, K, J, (float*)ws, ns, f16 != 0, st);
+            const int rc2 = launch_linear_fwd_256("linear_fwd_bf16(256)", 1, f16 != 0, (const __hip_bfloat16*)x_bf16, ldx, (const __hip_bfloat16*)w_bf16,
+                                                  M, K, J, (float*)ws, ns, st);
             if (rc2) return rc2;
-            return launch_splitk_reduce("linear_fwd_bf16(256).reduce", (const float*)ws, ns, (int64_t)M * J, efin, st);
+            return launch_splitk_reduce("linear_fwd_bf16(256).reduce", (const float*)ws, ns, (int64_t)M * J, efinal, st);
         }
     }
     const int nsplit = linear_splits_h(M, K, J);
     KCLoaderH::P ap{(const __hip_bfloat16*)x_bf16, ldx, M};
     KCLoaderH::P bp{(const __hip_bfloat16*)w_bf16, K, J};
-    EpiP efinal{(dropmask || mult_out) ? EPI_FULL : EPI_BIAS_RELU, y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult, 0};
     EpiP ep = efinal;
     if (nsplit > 1) {
         GN_REQUIRE(ws && aligned16(ws) && ws_bytes >= goalnet_linear_fwd_bf16_ws_bytes(M, K, J), GOALNET_E_WORKSPACE,
                    "linear_fwd_bf16: split-K needs a 16-byte aligned workspace of goalnet_linear_fwd_bf16_ws_bytes()");
-        ep = EpiP{EPI_RAW, (float*)ws, J, M, J, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)M * J};
+        ep = epi_slabs((float*)ws, M, J);
     }
     const int rc = launch_gemm_h<KCLoaderH, KCLoaderH>("linear_fwd_bf16", ap, bp, ep, M, J, (int)(K / BKH), nsplit, 0, f16 != 0, st);
     if (rc || nsplit == 1) return rc;
@@ -763,42 +760,37 @@ int goalnet_bf16_padded_layout(int N, int H, int W, int C, int64_t* total_elems,
     return 0;
 }
 
-int goalnet_to_bf16_padded(const float* x, const float* scale, const float* shift, void* y_pad, int N, int H, int W, int C, int f16, void* stream) {
-    GN_REQUIRE(x && y_pad, GOALNET_E_NULL, "to_bf16_padded: null pointer");
-    GN_REQUIRE((scale == nullptr) == (shift == nullptr), GOALNET_E_NULL, "to_bf16_padded: scale/shift must both be set or both NULL");
-    GN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, GOALNET_E_SHAPE, "to_bf16_padded: bad dims (C %% 8)");
-    GN_REQUIRE(aligned16(x) && aligned16(y_pad) && aligned16(scale) && aligned16(shift), GOALNET_E_ALIGN, "to_bf16_padded: alignment");
+static int to_padded_h16(const char* who, bool h16, const void* x, const float* scale, const float* shift, void* y_pad, int N, int H, int W, int C,
+                         int f16, void* stream) {
+    GN_REQUIRE(x && y_pad, GOALNET_E_NULL, "%s: null pointer", who);
+    GN_REQUIRE((scale == nullptr) == (shift == nullptr), GOALNET_E_NULL, "%s: scale/shift must both be set or both NULL", who);
+    GN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, GOALNET_E_SHAPE, "%s: bad dims (C %% 8)", who);
+    GN_REQUIRE(aligned16(x) && aligned16(y_pad) && aligned16(scale) && aligned16(shift), GOALNET_E_ALIGN, "%s: alignment", who);
     const int64_t n8 = (int64_t)N * H * W * (C / 8);
-    if (f16) hipLaunchKernelGGL((to_bf16_padded_kernel<false, true>), dim3(grid1d(n8)), dim3(256), 0, (hipStream_t)stream, (const void*)x, scale, shift,
-                                (__hip_bfloat16*)y_pad, n8, H, W, C);
-    else hipLaunchKernelGGL((to_bf16_padded_kernel<false, false>), dim3(grid1d(n8)), dim3(256), 0, (hipStream_t)stream, (const void*)x, scale, shift,
-                            (__hip_bfloat16*)y_pad, n8, H, W, C);
-    GN_LAUNCH_CHECK("to_bf16_padded");
+    const auto kernel = !h16 ? (f16 ? to_bf16_padded_kernel<false, true> : to_bf16_padded_kernel<false, false>)
+                             : (f16 ? to_bf16_padded_kernel<true, true> : to_bf16_padded_kernel<true, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid1d(n8)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, (__hip_bfloat16*)y_pad, n8, H, W, C);
+    GN_LAUNCH_CHECK(who);
     return 0;
 }
-
+int goalnet_to_bf16_padded(const float* x, const float* scale, const float* shift, void* y_pad, int N, int H, int W, int C, int f16, void* stream) {
+    return to_padded_h16("to_bf16_padded", false, x, scale, shift, y_pad, N, H, W, C, f16, stream);
+}
 int goalnet_to_bf16_padded_p16(const void* x_bf16, const float* scale, const float* shift, void* y_pad, int N, int H, int W, int C, int f16, void* stream) {
-    GN_REQUIRE(x_bf16 && y_pad, GOALNET_E_NULL, "to_bf16_padded_p16: null pointer");
-    GN_REQUIRE((scale == nullptr) == (shift == nullptr), GOALNET_E_NULL, "to_bf16_padded_p16: scale/shift must both be set or both NULL");
-    GN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, GOALNET_E_SHAPE, "to_bf16_padded_p16: bad dims (C %% 8)");
-    GN_REQUIRE(aligned16(x_bf16) && aligned16(y_pad) && aligned16(scale) && aligned16(shift), GOALNET_E_ALIGN, "to_bf16_padded_p16: alignment");
-    const int64_t n8 = (int64_t)N * H * W * (C / 8);
-    if (f16) hipLaunchKernelGGL((to_bf16_padded_kernel<true, true>), dim3(grid1d(n8)), dim3(256), 0, (hipStream_t)stream,
-                                x_bf16, scale, shift, (__hip_bfloat16*)y_pad, n8, H, W, C);
-    else hipLaunchKernelGGL((to_bf16_padded_kernel<true, false>), dim3(grid1d(n8)), dim3(256), 0, (hipStream_t)stream,
-                            x_bf16, scale, shift, (__hip_bfloat16*)y_pad, n8, H, W, C);
-    GN_LAUNCH_CHECK("to_bf16_padded_p16");
-    return 0;
+    return to_padded_h16("to_bf16_padded_p16", true, x_bf16, scale, shift, y_pad, N, H, W, C, f16, stream);
 }
 
 static int conv_splits_h(int64_t M, int Cin, int Cout) {
     return conv_fwd_splits(((M + BM - 1) / BM) * ((Cout + BN - 1) / BN), 9 * Cin / BKH);
 }
 
-// large problems: the 256 x 256 phased tile (gemm_bf16_256.hip); GOALNET_BF16_TILE=128 / 256 forces a choice (tests, A/B runs)
-static bool conv_use_256(int64_t M, int Cout) {
-    const char* forced = getenv("GOALNET_BF16_TILE");
-    return forced ? forced[0] == '2' : (Cout >= 256 && M >= 65536);
+// The kernel that serves goalnet_conv3x3_fwd_bf16p for M = N H W output pixels: large problems the 256 x 256 phased tile, <= 64
+// output channels the 128 x 64 tile (conv2's data gradient: 256 -> 64 channels; GOALNET_BF16_N64_OFF: A/B runs), else 128 x 128.
+// The launch, goalnet_conv3x3_fwd_bf16p_kernel_name and goalnet_conv3x3_fwd_bf16p_o16_ok all ask here.
+enum ConvRoute { CONV_256, CONV_128X64, CONV_128 };
+static ConvRoute conv_route(int64_t M, int Cout) {
+    if (use_256(Cout >= 256 && M >= 65536)) return CONV_256;
+    return Cout <= 64 && !getenv("GOALNET_BF16_N64_OFF") ? CONV_128X64 : CONV_128;
 }
 
 size_t goalnet_conv3x3_fwd_bf16p_ws_bytes(int N, int H, int W, int Cin, int Cout) {
@@ -819,20 +811,18 @@ int goalnet_conv3x3_fwd_bf16p(const void* x_pad, const void* w_bf16, const float
     hipStream_t st = (hipStream_t)stream;
     ConvAPadLoaderH::P ap{(const __hip_bfloat16*)x_pad, H, W, Cin, M};
     KCLoaderH::P bp{(const __hip_bfloat16*)w_bf16, (int64_t)9 * Cin, Cout};
-    const EpiP efinal{EPI_BIAS_RELU, y, Cout, (int)M, Cout, bias, relu, nullptr, 0, nullptr, 0, 0};
+    const EpiP efinal = epi_act(y, Cout, (int)M, Cout, bias, relu);
     EpiP ep = efinal;
-    // large problems: the 256 x 256 phased tile (gemm_bf16_256.hip); GOALNET_BF16_TILE=128 / 256 forces a choice (tests, A/B runs)
-    {
-        if (conv_use_256(M, Cout)) return launch_conv_bf16_256("conv3x3_fwd_bf16p(256)", (const __hip_bfloat16*)x_pad, H, W, Cin, M,
-                                             (const __hip_bfloat16*)w_bf16, Cout, efinal, f16 != 0, st);
-    }
+    const ConvRoute route = conv_route(M, Cout);
+    if (route == CONV_256) return launch_conv_256("conv3x3_fwd_bf16p(256)", 1, f16 != 0, (const __hip_bfloat16*)x_pad, H, W, Cin, M,
+                                                  (const __hip_bfloat16*)w_bf16, Cout, efinal, st);
     const int nsplit = ws ? conv_splits_h(M, Cin, Cout) : 1;
     if (nsplit > 1) {
         GN_REQUIRE(aligned16(ws) && ws_bytes >= goalnet_conv3x3_fwd_bf16p_ws_bytes(N, H, W, Cin, Cout), GOALNET_E_WORKSPACE,
                    "conv3x3_fwd_bf16p: workspace too small or misaligned");
-        ep = EpiP{EPI_RAW, (float*)ws, Cout, (int)M, Cout, nullptr, 0, nullptr, 0, nullptr, 0, M * Cout};
+        ep = epi_slabs((float*)ws, (int)M, Cout);
     }
-    const int rc = (Cout <= 64 && !getenv("GOALNET_BF16_N64_OFF"))       // 128 x 64 tile (conv2's data gradient: 256 -> 64 channels)
+    const int rc = route == CONV_128X64
         ? launch_gemm_h<ConvAPadLoaderH, KCLoaderH, true>("conv3x3_fwd_bf16p", ap, bp, ep, M, Cout, 9 * Cin / BKH, nsplit, 0, f16 != 0, st)
         : launch_gemm_h<ConvAPadLoaderH, KCLoaderH>("conv3x3_fwd_bf16p", ap, bp, ep, M, Cout, 9 * Cin / BKH, nsplit, 0, f16 != 0, st);
     if (rc || nsplit == 1) return rc;
@@ -847,15 +837,17 @@ extern "C" {
  * one (the data gradient): the dispatch above, not executed */
 const char* goalnet_conv3x3_fwd_bf16p_kernel_name(int N, int H, int W, int Cin, int Cout, int forward) {
     (void)Cin;
-    if (conv_use_256((int64_t)N * H * W, Cout)) return conv_bf16_256_kernel_name(forward ? 0 : 1);
-    return (Cout <= 64 && !getenv("GOALNET_BF16_N64_OFF")) ? gemm_bf16_kernel_name<ConvAPadLoaderH, KCLoaderH, false, true>()
-                                                            : gemm_bf16_kernel_name<ConvAPadLoaderH, KCLoaderH, false, false>();
+    switch (conv_route((int64_t)N * H * W, Cout)) {
+    case CONV_256: return conv_bf16_256_kernel_name(forward ? 0 : 1);
+    case CONV_128X64: return gemm_bf16_kernel_name<ConvAPadLoaderH, KCLoaderH, false, true>();
+    default: return gemm_bf16_kernel_name<ConvAPadLoaderH, KCLoaderH, false, false>();
+    }
 }
 
 /* 1 when goalnet_conv3x3_fwd_bf16p_o16 serves these dims (the shapes the 256 x 256 tile takes), else 0 */
 int goalnet_conv3x3_fwd_bf16p_o16_ok(int N, int H, int W, int Cin, int Cout) {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % BKH != 0 || Cout % 8 != 0) return 0;
-    return conv_use_256((int64_t)N * H * W, Cout) ? 1 : 0;
+    return conv_route((int64_t)N * H * W, Cout) == CONV_256 ? 1 : 0;
 }
 
 /* y_bf16[N][H][W][Cout] = bf16(act(conv3x3(x_pad, w) + bias)): the fp32 accumulator (+ bias, ReLU) is rounded once, at
@@ -870,9 +862,10 @@ int goalnet_conv3x3_fwd_bf16p_o16(const void* x_pad, const void* w_bf16, const f
     GN_REQUIRE((int64_t)N * (H + 2) * (W + 2) < (1ll << 31) - 4096, GOALNET_E_SHAPE, "conv3x3_fwd_bf16p_o16: too many pixels");
     GN_REQUIRE(goalnet_conv3x3_fwd_bf16p_o16_ok(N, H, W, Cin, Cout), GOALNET_E_SHAPE,
                "conv3x3_fwd_bf16p_o16: dims not served (ask goalnet_conv3x3_fwd_bf16p_o16_ok; use goalnet_conv3x3_fwd_bf16p)");
-    const EpiP ep{EPI_BIAS_RELU, nullptr, Cout, (int)M, Cout, bias, relu, nullptr, 0, nullptr, 0, 0, y_bf16};
-    return launch_conv_bf16_256("conv3x3_fwd_bf16p_o16(256)", (const __hip_bfloat16*)x_pad, H, W, Cin, M, (const __hip_bfloat16*)w_bf16,
-                                Cout, ep, f16 != 0, (hipStream_t)stream);
+    EpiP ep = epi_act(nullptr, Cout, (int)M, Cout, bias, relu);
+    ep.out16 = y_bf16;
+    return launch_conv_256("conv3x3_fwd_bf16p_o16(256)", 1, f16 != 0, (const __hip_bfloat16*)x_pad, H, W, Cin, M, (const __hip_bfloat16*)w_bf16,
+                           Cout, ep, (hipStream_t)stream);
 }
 
 static int wgrad_splits_h(int64_t Mp, int Cin, int Cout) {
@@ -888,17 +881,15 @@ static int wgrad_splits_h(int64_t Mp, int Cin, int Cout) {
 
 // large problems reduce on the 256 x 256 phased tile (gemm_bf16_256.hip); GOALNET_BF16_TILE=128 / 256 forces a choice
 static bool wgrad_use_256(int64_t Mp, int Cin, int Cout) {
-    const char* forced = getenv("GOALNET_BF16_TILE");
-    if (forced) return forced[0] == '2';
     // 256 x 256 tiles must cover the [Cout][9 Cin] output with >= 70 % useful area (conv2: 256 x 576 -> 3 tiles, 75 %;
     // measured 914 TF/s of useful work there against 513 on 128 x 128 tiles)
     const int64_t covered = (int64_t)((Cout + 255) / 256) * ((9 * Cin + 255) / 256) * 65536;
-    return Cout >= 256 && Mp >= 262144 && (int64_t)Cout * 9 * Cin * 10 >= covered * 7;
+    return use_256(Cout >= 256 && Mp >= 262144 && (int64_t)Cout * 9 * Cin * 10 >= covered * 7);
 }
 
 size_t goalnet_conv3x3_wgrad_bf16_ws_bytes(int N, int H, int W, int Cin, int Cout) {
     const int64_t Mp = (int64_t)N * (H + 2) * (W + 2);
-    const int a = wgrad_splits_h(Mp, Cin, Cout), b = wgrad_splits_256(Mp, Cin, Cout);       // enough for either kernel
+    const int a = wgrad_splits_h(Mp, Cin, Cout), b = wgrad_splits_256(1, Mp, Cin, Cout);    // enough for either kernel
     return (size_t)(a > b ? a : b) * (size_t)Cout * 9 * Cin * sizeof(float);
 }
 
@@ -914,22 +905,20 @@ int goalnet_conv3x3_wgrad_bf16(const void* x_pad, const void* dy_pad, float* dw,
     GN_REQUIRE(ws_bytes >= goalnet_conv3x3_wgrad_bf16_ws_bytes(N, H, W, Cin, Cout), GOALNET_E_WORKSPACE, "conv3x3_wgrad_bf16: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int64_t slab = (int64_t)Cout * 9 * Cin;
+    const EpiP er = epi_raw(dw, (int64_t)9 * Cin, Cout, 9 * Cin);          // of the reduction
     if (wgrad_use_256(Mp, Cin, Cout)) {
-        const int ns = wgrad_splits_256(Mp, Cin, Cout);
-        const int rc = launch_wgrad_bf16_256("conv3x3_wgrad_bf16(256)", (const __hip_bfloat16*)x_pad, (const __hip_bfloat16*)dy_pad, W + 2,
-                                             Cin, Cout, Mp, (float*)ws, ns, f16 != 0, st);
+        const int ns = wgrad_splits_256(1, Mp, Cin, Cout);
+        const int rc = launch_wgrad_256("conv3x3_wgrad_bf16(256)", 1, f16 != 0, (const __hip_bfloat16*)x_pad, (const __hip_bfloat16*)dy_pad, W + 2,
+                                        Cin, Cout, Mp, (float*)ws, ns, st);
         if (rc) return rc;
-        EpiP er{EPI_RAW, dw, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, 0};
         return launch_splitk_reduce("conv3x3_wgrad_bf16(256).reduce", (const float*)ws, ns, slab, er, st);
     }
     const int nsplit = wgrad_splits_h(Mp, Cin, Cout);
     const int ktiles = (int)((Mp + BKH - 1) / BKH);
     MCLoaderH::P ap{(const __hip_bfloat16*)dy_pad, Cout, Cout, (int)Mp};
     ConvWgradBLoaderH::P bp{(const __hip_bfloat16*)x_pad, W + 2, Cin, Mp};
-    EpiP ep{EPI_RAW, (float*)ws, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, slab};
-    const int rc = launch_gemm_h<MCLoaderH, ConvWgradBLoaderH>("conv3x3_wgrad_bf16", ap, bp, ep, Cout, 9 * Cin, ktiles, nsplit, 1, f16 != 0, st);
+    const int rc = launch_gemm_h<MCLoaderH, ConvWgradBLoaderH>("conv3x3_wgrad_bf16", ap, bp, epi_slabs((float*)ws, Cout, 9 * Cin), Cout, 9 * Cin, ktiles, nsplit, 1, f16 != 0, st);
     if (rc) return rc;
-    EpiP er{EPI_RAW, dw, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, 0};
     return launch_splitk_reduce("conv3x3_wgrad_bf16.reduce", (const float*)ws, nsplit, slab, er, st);
 }
 
@@ -942,12 +931,11 @@ int goalnet_linear_bwd_dx_bf16(const void* dy_bf16, int64_t lddy, const void* w_
     GN_REQUIRE(lddy % 8 == 0 && lddx % 4 == 0, GOALNET_E_ALIGN, "linear_bwd_dx_bf16: leading dimensions must be multiples of 16 bytes (lddy %% 8, lddx %% 4)");
     GN_REQUIRE(aligned16(dy_bf16) && aligned16(w_bf16) && aligned16(dx), GOALNET_E_ALIGN, "linear_bwd_dx_bf16: alignment");
     if (!mult && linear_use_256(M, K, J))
-        return launch_linear_dx_bf16_256("linear_bwd_dx_bf16(256)", (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)w_bf16, M, K,
-                                         J, dx, nullptr, lddx, f16 != 0, (hipStream_t)stream);
+        return launch_linear_dx_256("linear_bwd_dx_bf16(256)", 1, f16 != 0, (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)w_bf16, M, K,
+                                    J, dx, nullptr, lddx, nullptr, (hipStream_t)stream);
     KCLoaderH::P ap{(const __hip_bfloat16*)dy_bf16, lddy, M};
     MCLoaderH::P bp{(const __hip_bfloat16*)w_bf16, K, (int)K, J};
-    EpiP ep{mult ? EPI_MUL : EPI_RAW, dx, lddx, M, (int)K, nullptr, 0, mult, ldmult, nullptr, 0, 0};
-    return launch_gemm_h<KCLoaderH, MCLoaderH>("linear_bwd_dx_bf16", ap, bp, ep, M, K, J / BKH, 1, 1, f16 != 0, (hipStream_t)stream);
+    return launch_gemm_h<KCLoaderH, MCLoaderH>("linear_bwd_dx_bf16", ap, bp, epi_mul(dx, lddx, M, (int)K, mult, ldmult), M, K, J / BKH, 1, 1, f16 != 0, (hipStream_t)stream);
 }
 
 /* 1 when goalnet_linear_bwd_dx_bf16_o16 serves these dims (the shapes the 256 x 256 tile takes), else 0 */
@@ -965,8 +953,8 @@ int goalnet_linear_bwd_dx_bf16_o16(const void* dy_bf16, int64_t lddy, const void
     GN_REQUIRE(aligned16(dy_bf16) && aligned16(w_bf16) && aligned16(dx_bf16), GOALNET_E_ALIGN, "linear_bwd_dx_bf16_o16: alignment");
     GN_REQUIRE(goalnet_linear_bwd_dx_bf16_o16_ok(M, K, J), GOALNET_E_SHAPE,
                "linear_bwd_dx_bf16_o16: dims not served (ask goalnet_linear_bwd_dx_bf16_o16_ok; use goalnet_linear_bwd_dx_bf16)");
-    return launch_linear_dx_bf16_256("linear_bwd_dx_bf16_o16(256)", (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)w_bf16, M, K,
-                                     J, nullptr, (__hip_bfloat16*)dx_bf16, lddx, f16 != 0, (hipStream_t)stream);
+    return launch_linear_dx_256("linear_bwd_dx_bf16_o16(256)", 1, f16 != 0, (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)w_bf16, M, K,
+                                J, nullptr, (__hip_bfloat16*)dx_bf16, lddx, nullptr, (hipStream_t)stream);
 }
 
 /* dw[j][k] = sum_m dy_bf16[m][j] * x_bf16[m][k]   (fp32 out) */
@@ -977,19 +965,15 @@ int goalnet_linear_bwd_dw_bf16(const void* dy_bf16, int64_t lddy, const void* x_
     GN_REQUIRE(J % 8 == 0 && K % 8 == 0, GOALNET_E_SHAPE, "linear_bwd_dw_bf16: J, K %% 8");
     GN_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0, GOALNET_E_ALIGN, "linear_bwd_dw_bf16: leading dimensions must be multiples of 16 bytes (lddy %% 8, ldx %% 8)");
     GN_REQUIRE(aligned16(dy_bf16) && aligned16(x_bf16) && aligned16(dw), GOALNET_E_ALIGN, "linear_bwd_dw_bf16: alignment");
-    {
-        // >= 256 output rows, a reduction of at least 4 K-tiles and an output wide enough to fill the chip with 256^2 tiles
-        const char* forced = getenv("GOALNET_BF16_TILE");
-        const bool big = forced ? forced[0] == '2' : (J >= 256 && M >= 256 && K >= (1 << 18));
-        if (big) return launch_linear_dw_bf16_256("linear_bwd_dw_bf16(256)", (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)x_bf16,
-                                                  ldx, M, K, J, dw, f16 != 0, (hipStream_t)stream);
-    }
+    // >= 256 output rows, a reduction of at least 4 K-tiles and an output wide enough to fill the chip with 256^2 tiles
+    if (use_256(J >= 256 && M >= 256 && K >= (1 << 18)))
+        return launch_linear_dw_256("linear_bwd_dw_bf16(256)", 1, f16 != 0, (const __hip_bfloat16*)dy_bf16, lddy, (const __hip_bfloat16*)x_bf16, ldx,
+                                    M, K, J, dw, nullptr, (hipStream_t)stream);
     MCLoaderH::P ap{(const __hip_bfloat16*)dy_bf16, lddy, J, M};
     MCLoaderH::P bp{(const __hip_bfloat16*)x_bf16, ldx, (int)K, M};
-    EpiP ep{EPI_RAW, dw, K, J, (int)K, nullptr, 0, nullptr, 0, nullptr, 0, 0};
     // measured at M = 1024, K = 2.5 M: 3.8 ms with one stage and 4 blocks per CU vs 4.7 ms with two stages and 2 (the data
     // gradient, whose W tiles are 256-B pieces 5 MB apart, is the other way round: 10.2 vs 6.6 ms, and keeps two stages)
-    return launch_gemm_h_1stage<MCLoaderH, MCLoaderH>("linear_bwd_dw_bf16", ap, bp, ep, J, K, (M + BKH - 1) / BKH, 1, f16 != 0, (hipStream_t)stream);
+    return launch_gemm_h_1stage<MCLoaderH, MCLoaderH>("linear_bwd_dw_bf16", ap, bp, epi_raw(dw, K, J, (int)K), J, K, (M + BKH - 1) / BKH, 1, f16 != 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

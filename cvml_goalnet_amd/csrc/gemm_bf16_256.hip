@@ -34,11 +34,14 @@
 // the bias of the next tile's columns is fetched there too. In-kernel stamps (scripts/stamps_conv.py, conv3 forward, random
 // operands): tile period 66.7 us = main loop 57.5 + prologue issue / MFMA drain 2.1 + epilogue 4.3 + waves re-joining 1.9
 // + bias 0.7 + 0.2; the one-block-per-tile form paid a block dispatch, the loaders' set-up and the first DMA latency
-// in front of every tile (~3 us more). The convolution forward / data gradient feed the MFMA (B, A) instead of (A, B): the
-// accumulators hold C^T blocks, a lane owns 4 consecutive columns of one output row, and the epilogue packs and stores
-// without transposing (SWAP below; bit-identical results, scripts/probe/swap_hash.py). What is left of the epilogue is
+// in front of every tile (~3 us more). The roles with a 16-bit result (convolution forward / data gradient, linear5's dX) feed
+// the MFMA (B, A) instead of (A, B): the accumulators hold C^T blocks, a lane owns 4 consecutive columns of one output row, and
+// the epilogue packs and stores without transposing (SWAP below; bit-identical to the (A, B) order, which these roles no longer
+// have a build of; scripts/probe/swap_hash.py hashes every contraction for such comparisons). What is left of the epilogue is
 // the stores themselves: the CUs run in step, so 256 x 128 KB leave at the same time (a store pattern of whole 128-B lines
 // per 8 lanes, tried as a timing experiment, moved the total by < 1 us).
+#include <type_traits>
+
 #include "gemm_bf16_common.h"
 
 using namespace goalnet;
@@ -333,9 +336,6 @@ __device__ __forceinline__ void mfma_pinned(f32x16& c, const bf16x8& a, const bf
 // roles whose launch is persistent (one block per CU walking the tiles); see launch_256_t for the measurements
 constexpr bool walks_tiles(int role) { return role == 0 || role == 1 || role == 4; }
 
-#ifndef GN_SWAP_OPERANDS
-#define GN_SWAP_OPERANDS 1          // 0: the (A, B) operand order with the transposing epilogue (A/B builds only)
-#endif
 #ifdef GN_STAMPS
 // Diagnostic build only (-DGN_STAMPS, loaded through GOALNET_LIB_PATH by scripts/ablate_conv.py): wave 0 of every block
 // stamps the 100 MHz real-time counter at six points of every tile (0 tile start, 1 bias staged, 2 first operands landed,
@@ -358,11 +358,11 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
     // accumulators, without the quad transposes that were half of its ~1100 VALU instructions per wave.
     // Transposed-read operands keep their row / column permutation: it applies to the index inside the 32-block, which SWAP
     // moves from the lane to the register (columns) and from the register to the lane (rows).
-    // Only the roles with a 16-bit result use it (same box, bench step: conv forward -5.8 %, data gradient -3.0 %, linear5 dX
+    // Only the roles with a 16-bit result use it, and always (same box, bench step: conv forward -5.8 %, data gradient -3.0 %, linear5 dX
     // -2 % together with the tile walk). The fp32 slab roles keep (A, B): their transposed stores are whole 128-B lines per 8
     // lanes, the swapped form writes 32-B pieces of 32 rows per instruction, and linear5's dW (256 KB of fp32 per 16 K-tiles)
-    // lost 7 % with it; the weight gradient and linear5's forward did not move.
-    constexpr bool SWAP = GN_SWAP_OPERANDS && (ROLE == 0 || ROLE == 1 || ROLE == 4);
+    // lost 7 % with it; the weight gradient and linear5's forward did not move. Those roles carry no bias, no ReLU and no 16-bit result.
+    constexpr bool SWAP = ROLE == 0 || ROLE == 1 || ROLE == 4;
     // WALK: the block goes on to the virtual blocks L + gridDim.x, ... (launch_256_t launches one block per CU for these roles);
     // the other roles run one tile per block and compile without the hand-over (no register pressure from it, no spills).
     constexpr bool WALK = walks_tiles(ROLE);
@@ -401,28 +401,20 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
     al.issue(kt0 + 0, 0, slot(0, 0)); bl.issue(kt0 + 0, 0, slot(0, 2)); bl.issue(kt0 + 0, 1, slot(0, 3)); al.issue(kt0 + 0, 1, slot(0, 1)); \
     bl.issue(kt0 + 1, 0, slot(1, 2)); al.issue(kt0 + 1, 0, slot(1, 0)); bl.issue(kt0 + 1, 1, slot(1, 3));
 
-    // bias of the tile's 256 columns (convolution forward). SWAP: register e of acc[.][j] is output column
+    // bias of the tile's 256 columns (convolution forward, a SWAP role): register e of acc[.][j] is output column
     // 32 j + (e & 3) + 8 (e >> 2) + 4 (lane >> 5) of the wave's 64 — 32 different values per lane: thread t fetches column t
     // while the previous tile's epilogue runs (one register), the tile start puts it into LDS (1 KB beside the 128 KB of
-    // operands) and the accumulators are initialised from there. Otherwise all 16 registers of acc[.][j] are column
-    // 32 j + (lane & 31): two registers.
+    // operands) and the accumulators are initialised from there.
     // two copies, used alternately by consecutive tiles: a wave that is already at the top of the next tile writes the OTHER copy while a
     // slower wave may still be reading this tile's in its epilogue (LATE_BIAS); waves are never more than one tile apart (the phases'
     // barriers keep them together inside a tile)
     __shared__ __attribute__((aligned(16))) float bias_lds[2][T];
     int bias_par = 0;
-    float bias_t = 0.f, bias_col[2] = {0.f, 0.f};
+    float bias_t = 0.f;
 #define GN_LOAD_BIAS()                                                                                      \
     if constexpr (ROLE == 0) {                                                                              \
-        if constexpr (SWAP) {                                                                               \
-            bias_t = 0.f;                                                                                   \
-            if (ep.bias && tid < T && tn * T + tid < ep.cols) bias_t = ep.bias[tn * T + tid];               \
-        } else {                                                                                            \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                 \
-                const int colj = tn * T + wc * 64 + j * 32 + (lane & 31);                                   \
-                bias_col[j] = ep.bias && colj < ep.cols ? ep.bias[colj] : 0.f;                              \
-            }                                                                                               \
-        }                                                                                                   \
+        bias_t = 0.f;                                                                                       \
+        if (ep.bias && tid < T && tn * T + tid < ep.cols) bias_t = ep.bias[tn * T + tid];                   \
     }
 
     int vb = (int)blockIdx.x;
@@ -438,7 +430,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
     if constexpr (SWAP) GN_WAIT_KTILE0()
   for (;;) {
     GN_STAMP(0)
-    if constexpr (SWAP && ROLE == 0) {
+    if constexpr (ROLE == 0) {
         if (tid < T) bias_lds[bias_par][tid] = bias_t;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -449,7 +441,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
     // stores, so that it does not wait for those stores' acknowledgements here: 1.5 us per tile in the stamps).
     if constexpr (!SWAP) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
-    // The accumulators start at the bias, so the epilogue has no add left.
+    // The accumulators of the convolution forward start at the bias, so its epilogue has no add left; the others start at zero.
     f32x16 acc[4][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -467,7 +459,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = bias_col[j];
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
         }
     }
     GN_STAMP(2)
@@ -558,10 +550,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
     GN_STAMP(4)
     do {                                            // the epilogue of tile (tm_out, tn_out, split_out); `break` = done
     const int tm = tm_out, tn = tn_out, split = split_out;
-    // epilogue (conv forward: bias + ReLU; data gradient: raw; weight gradient / linear5 forward: raw split-K slab).
-    // A lane of the 32x32 accumulator holds 4 consecutive ROWS of one column per register group; quad_transpose4
-    // (gemm_common.h) turns that into 4 consecutive COLUMNS of one row, i.e. one 16-byte store per lane and whole 128-B lines
-    // per quad row: 32 store instructions per wave instead of 128 (the tail of a 256 x 256 fp32 tile is store-issue-bound).
+    // epilogue (conv forward: bias + ReLU; data gradient, linear5 dX: raw, fp32 or 16-bit; weight gradient / linear5 forward: raw
+    // split-K slab; linear5 dW: raw). The SWAP roles store straight from the accumulators; the others (fp32 only) transpose first.
     const int r = lane & 31, hh = lane >> 5;
     // what is left to do per value: ROLE 0 (conv forward) clamps at 0 when ReLU is on (its bias is already in); the
     // other roles store the accumulator as it is (their callers pass no bias and no ReLU)
@@ -648,49 +638,11 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
         GN_STAMP(5)
         break;
     }
+    // Roles 2, 3, 5 (fp32, no bias, no ReLU): a lane of the 32x32 accumulator holds 4 consecutive ROWS of one column per register
+    // group; quad_transpose4 (gemm_common.h) turns that into 4 consecutive COLUMNS of one row, i.e. one 16-byte store per lane and
+    // whole 128-B lines per quad row: 32 store instructions per wave instead of 128 (the tail of a 256 x 256 fp32 tile is
+    // store-issue-bound).
     const int r4 = r & ~3;
-    if constexpr (ROLE == 0 || ROLE == 1 || ROLE == 4) {
-        // bf16 result (a conv output on its way to the max-pool, or the gradient wrt a BatchNorm output; both are only read
-        // by HBM-bound passes): after the quad transpose
-        // lanes l and l ^ 4 hold columns c..c+3 and c+4..c+7 of the same rows for two register groups (rows 8 apart);
-        // they swap one packed group so that each stores 8 consecutive bf16 (16 B) of ONE row: 16 store instructions
-        // per wave for the tile (the fp32 form needs 32) and half the bytes.
-        if (ep.out16) {
-            __hip_bfloat16* o16 = reinterpret_cast<__hip_bfloat16*>(ep.out16);
-            const int hi = (lane >> 2) & 1;
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    const int col4 = tn * T + (TRB ? ni * 128 + 16 * wc + (r4 & 15) + 64 * (r4 >> 4) : wc * 64 + ni * 32 + r4);
-                    const int col8 = col4 - 4 * hi;                                                    // first of this lane's 8 columns
-                    const bool colok = col8 < ep.cols;                                                 // cols % 8 == 0
-#pragma unroll
-                    for (int gp = 0; gp < 2; ++gp) {
-                        unsigned pk[2][2];
-#pragma unroll
-                        for (int k = 0; k < 2; ++k) {
-                            const int g = 2 * gp + k;
-                            float n0 = acc[mi][ni][4 * g], n1 = acc[mi][ni][4 * g + 1], n2 = acc[mi][ni][4 * g + 2], n3 = acc[mi][ni][4 * g + 3];
-                            quad_transpose4(n0, n1, n2, n3, lane);
-                            pk[k][0] = pack2_h16<F16>(fin(n0), fin(n1));
-                            pk[k][1] = pack2_h16<F16>(fin(n2), fin(n3));
-                        }
-                        // lane hi = 0 keeps group 2gp and gets the partner's 2gp (its columns + 4); hi = 1 keeps 2gp + 1
-                        const unsigned s0 = hi ? pk[0][0] : pk[1][0], s1 = hi ? pk[0][1] : pk[1][1];
-                        const unsigned q0 = (unsigned)__shfl_xor((int)s0, 4, 64), q1 = (unsigned)__shfl_xor((int)s1, 4, 64);
-                        const unsigned m0 = hi ? pk[1][0] : pk[0][0], m1 = hi ? pk[1][1] : pk[0][1];
-                        const int i = (lane & 3) + 8 * (2 * gp + hi) + 4 * hh;
-                        const int64_t row = (int64_t)tm * T + (TRA ? (mi >> 1) * 128 + 16 * (2 * wr + (mi & 1)) + (i & 15) + 64 * (i >> 4)
-                                                                   : wr * 128 + (mi >> 1) * 64 + (mi & 1) * 32 + i);
-                        if (colok && row < ep.rows)
-                            *reinterpret_cast<uint4*>(o16 + row * ep.ld + col8) = hi ? make_uint4(q0, q1, m0, m1) : make_uint4(m0, m1, q0, q1);
-                    }
-                }
-            GN_STAMP(5)
-            break;
-        }
-    }
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -719,6 +671,34 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_256_kernel(typename AL::P ap
 #undef GN_WAIT_KTILE0
 #undef GN_LOAD_BIAS
 }
+
+// The kernels of this file: every operand form of every role, in the order they stand in the code object. The launchers below
+// instantiate exactly these; stating them here keeps that order, and with it the code object's sections, independent of how the
+// host code is arranged (scripts/codeobj_sections.py compares them across host-side changes).
+template <int NSEG> using ConvA256 = ConvAPadLoader256<64, NSEG>;
+template <int NSEG> using KCA256 = KCLoader256<64, NSEG>;
+template <int NSEG> using KCB256 = KCLoader256<32, NSEG>;
+#define GN_KERNEL_256(AL, BL, ROLE, F16) \
+    template __global__ void gemm_bf16_256_kernel<AL, BL, ROLE, F16>(typename AL::P, typename BL::P, EpiP, int, int, int, int, int, int);
+#define GN_KERNEL_256_PLAIN(AL, BL, ROLE) GN_KERNEL_256(AL, BL, ROLE, true) GN_KERNEL_256(AL, BL, ROLE, false)
+GN_KERNEL_256_PLAIN(ConvA256<0>, KCB256<0>, 0)
+GN_KERNEL_256_PLAIN(ConvA256<0>, KCB256<0>, 1)
+GN_KERNEL_256_PLAIN(KCA256<0>, KCB256<0>, 3)
+GN_KERNEL_256_PLAIN(KCA256<0>, MCLoader256T<0>, 4)
+GN_KERNEL_256_PLAIN(MCLoader256T<0>, MCLoader256T<0>, 5)
+GN_KERNEL_256_PLAIN(MCLoader256T<0>, ConvWgradBLoader256T<0>, 2)
+#define GN_KERNEL_256_SPLIT(AL, BL, ROLE) GN_KERNEL_256(AL<6>, BL<6>, ROLE, false) GN_KERNEL_256(AL<3>, BL<3>, ROLE, true)
+GN_KERNEL_256(ConvA256<6>, KCB256<6>, 0, false)
+GN_KERNEL_256(ConvA256<6>, KCB256<6>, 1, false)
+GN_KERNEL_256(ConvA256<3>, KCB256<3>, 0, true)
+GN_KERNEL_256(ConvA256<3>, KCB256<3>, 1, true)
+GN_KERNEL_256_SPLIT(MCLoader256T, ConvWgradBLoader256T, 2)
+GN_KERNEL_256_SPLIT(KCA256, KCB256, 3)
+GN_KERNEL_256_SPLIT(KCA256, MCLoader256T, 4)
+GN_KERNEL_256_SPLIT(MCLoader256T, MCLoader256T, 5)
+#undef GN_KERNEL_256_SPLIT
+#undef GN_KERNEL_256_PLAIN
+#undef GN_KERNEL_256
 
 }  // namespace
 
@@ -760,37 +740,50 @@ static int launch_256_t(const char* name, const typename AL::P& ap, const typena
     GN_LAUNCH_CHECK(name);
     return 0;
 }
-template <class AL, class BL, int ROLE>
-static int launch_256(const char* name, const typename AL::P& ap, const typename BL::P& bp, const EpiP& ep, int64_t tiles_m,
-                      int64_t tiles_n, int nsplit, int m_fast, int ktiles, int kps, bool f16, hipStream_t st) {
-    return f16 ? launch_256_t<AL, BL, ROLE, true>(name, ap, bp, ep, tiles_m, tiles_n, nsplit, m_fast, ktiles, kps, st)
-               : launch_256_t<AL, BL, ROLE, false>(name, ap, bp, ep, tiles_m, tiles_n, nsplit, m_fast, ktiles, kps, st);
-}
-
 template <class AL, class BL, int ROLE, bool F16> static const char* gemm_bf16_256_kernel_name() { return __PRETTY_FUNCTION__; }
 const char* conv_bf16_256_kernel_name(int role) {
-    return role == 0 ? gemm_bf16_256_kernel_name<ConvAPadLoader256<64>, KCLoader256<32>, 0, false>()
-                     : gemm_bf16_256_kernel_name<ConvAPadLoader256<64>, KCLoader256<32>, 1, false>();
+    return role == 0 ? gemm_bf16_256_kernel_name<ConvA256<0>, KCB256<0>, 0, false>() : gemm_bf16_256_kernel_name<ConvA256<0>, KCB256<0>, 1, false>();
 }
 
-// conv 3x3 forward (bias + ReLU epilogue) / data gradient (raw epilogue) on zero-padded 16-bit activations, 256^2 phased tile
-int launch_conv_bf16_256(const char* name, const __hip_bfloat16* x_pad, int H, int W, int Cin, int64_t M, const __hip_bfloat16* w,
-                         int Cout, const EpiP& ep, bool f16, hipStream_t st) {
-    typedef ConvAPadLoader256<64> AL;
-    typedef KCLoader256<32> BL;
-    const int64_t tiles_m = (M + T - 1) / T, tiles_n = (Cout + T - 1) / T;
-    AL::P ap{x_pad, H, W, Cin, M, 0, 0u};
-    BL::P bp{w, (int64_t)9 * Cin, Cout, Cin, 0, 0u};
-    const int kt = 9 * Cin / BKH;
-    // ROLE 0 carries the bias (in its accumulator start) and the optional ReLU; ROLE 1 stores raw accumulators
-    return ep.mode == EPI_BIAS_RELU && (ep.relu || ep.bias) ? launch_256<AL, BL, 0>(name, ap, bp, ep, tiles_m, tiles_n, 1, 0, kt, kt, f16, st)
-                                                            : launch_256<AL, BL, 1>(name, ap, bp, ep, tiles_m, tiles_n, 1, 0, kt, kt, f16, st);
+// ---- operand forms. parts = 1: plain 16-bit operands, bf16 or fp16 as the caller says. Split operands are the same kernels over NSEG
+// K-segments of [hi | mid | lo] (parts = 3, "bf16x6": bf16 triples, 6 segments) or [hi | mid] (parts = 2, "fp16x3": scaled fp16 pairs,
+// 3 segments, ep.oscale) stored side by side (comment at SEGMAP_A); their 16-bit format follows from `parts`. A plain operand is
+// the split operand with one part and no segment map (NSEG = 0: the loaders compile without the segment arithmetic and never look at
+// the segment fields of their parameters).
+template <int NSEG> struct SegCfg;
+template <> struct SegCfg<0> { static constexpr int NSEG = 0, KSEG = 1, PARTS = 1; static constexpr unsigned A = 0u, B = 0u; };
+template <> struct SegCfg<3> { static constexpr int NSEG = 3, KSEG = 3, PARTS = 2; static constexpr unsigned A = SEGMAP_A3, B = SEGMAP_B3; };
+template <> struct SegCfg<6> { static constexpr int NSEG = 6, KSEG = 6, PARTS = 3; static constexpr unsigned A = SEGMAP_A, B = SEGMAP_B; };
+static int kseg_of(int parts) { return parts == 1 ? 1 : parts == 3 ? 6 : 3; }           // K-tiles per 64 values of the reduction index
+
+// calls body(SegCfg of `parts`, F16 as a std::bool_constant): F16 is the caller's choice for plain operands only, so exactly the
+// kernels of the three operand forms are instantiated
+template <class Body>
+static int with_operands(int parts, bool f16, Body&& body) {
+    if (parts == 1) return f16 ? body(SegCfg<0>{}, std::true_type{}) : body(SegCfg<0>{}, std::false_type{});
+    return parts == 3 ? body(SegCfg<6>{}, std::false_type{}) : body(SegCfg<3>{}, std::true_type{});
+}
+
+// conv 3x3 forward (bias and / or ReLU: ROLE 0, the bias in the accumulator start) / data gradient (raw: ROLE 1) on zero-padded 16-bit
+// activations: x_pads = [pixels][parts Cin], ws = [Cout][9][parts Cin]
+int launch_conv_256(const char* name, int parts, bool f16, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M,
+                    const __hip_bfloat16* ws, int Cout, const EpiP& ep, hipStream_t st) {
+    return with_operands(parts, f16, [&](auto S, auto F16) {
+        typedef ConvA256<S.NSEG> AL;
+        typedef KCB256<S.NSEG> BL;
+        const int64_t tiles_m = (M + T - 1) / T, tiles_n = (Cout + T - 1) / T;
+        typename AL::P ap{x_pads, H, W, S.PARTS * Cin, M, Cin, S.A};
+        typename BL::P bp{ws, (int64_t)9 * S.PARTS * Cin, Cout, S.PARTS * Cin, Cin, S.B};
+        const int kt = 9 * S.KSEG * Cin / BKH;
+        return ep.mode == EPI_BIAS_RELU && (ep.relu || ep.bias) ? launch_256_t<AL, BL, 0, F16.value>(name, ap, bp, ep, tiles_m, tiles_n, 1, 0, kt, kt, st)
+                                                                : launch_256_t<AL, BL, 1, F16.value>(name, ap, bp, ep, tiles_m, tiles_n, 1, 0, kt, kt, st);
+    });
 }
 
 // split count of the weight gradient on 256 x 256 tiles: ~2048 blocks, a whole number of 256-CU rounds where possible
-int wgrad_splits_256(int64_t Mp, int Cin, int Cout) {
+int wgrad_splits_256(int parts, int64_t Mp, int Cin, int Cout) {
     const int64_t tiles = (int64_t)((Cout + T - 1) / T) * ((9 * Cin + T - 1) / T);
-    const int ktiles = (int)((Mp + BKH - 1) / BKH);
+    const int ktiles = kseg_of(parts) * (int)((Mp + BKH - 1) / BKH);
     int64_t s = (2048 + tiles - 1) / tiles;
     const int64_t smax = ktiles / 64 > 1 ? ktiles / 64 : 1;             // >= 64 K-tiles per split: the 7-half-tile prologue stays < 3 %
     if (s > smax) s = smax;
@@ -801,7 +794,28 @@ int wgrad_splits_256(int64_t Mp, int Cin, int Cout) {
     return (ktiles + kps - 1) / kps;
 }
 
-static int splits_for_256(int64_t tiles, int ktiles) {
+// conv 3x3 weight gradient on the zero-padded pixel grid: dy_pads = [padded pixels][parts Cout], x_pads = [padded pixels][parts Cin];
+// slabs[split][Cout][9 Cin] (fp32), reduced by the caller
+int launch_wgrad_256(const char* name, int parts, bool f16, const __hip_bfloat16* x_pads, const __hip_bfloat16* dy_pads, int Wp2, int Cin,
+                     int Cout, int64_t Mp, float* slabs, int nsplit, hipStream_t st) {
+    GN_REQUIRE(nsplit >= 1 && nsplit <= 65535, GOALNET_E_SHAPE, "%s: bad split count %d", name, nsplit);
+    return with_operands(parts, f16, [&](auto S, auto F16) {
+        typedef MCLoader256T<S.NSEG> AL;
+        typedef ConvWgradBLoader256T<S.NSEG> BL;
+        const int64_t tiles_m = (Cout + T - 1) / T, tiles_n = (9 * Cin + T - 1) / T;
+        const int seg_kt = (int)((Mp + BKH - 1) / BKH), ktiles = S.KSEG * seg_kt;
+        const int kps = (ktiles + nsplit - 1) / nsplit;
+        typename AL::P ap{dy_pads, (int64_t)S.PARTS * Cout, Cout, Mp, seg_kt, Cout, S.A};
+        typename BL::P bp{x_pads, Wp2, Cin, Mp, S.PARTS * Cin, seg_kt, S.B};
+        return launch_256_t<AL, BL, 2, F16.value>(name, ap, bp, epi_slabs(slabs, Cout, 9 * Cin), tiles_m, tiles_n, nsplit, 1, ktiles, kps, st);
+    });
+}
+
+// ---- linear5: x [M][parts K] (row stride ldx), w [J][parts K], dy [M][parts J] (row stride lddy); parts side by side along the row
+// split count of the forward: ~1024 blocks, >= 64 K-tiles per split, whole XCD groups
+int linear_fwd_splits_256(int parts, int M, int64_t K, int J) {
+    const int64_t tiles = (int64_t)((M + T - 1) / T) * ((J + T - 1) / T);
+    const int ktiles = (int)(kseg_of(parts) * K / BKH);
     int64_t s = (1024 + tiles - 1) / tiles;
     const int64_t smax = ktiles / 64 > 1 ? ktiles / 64 : 1;             // >= 64 K-tiles per split
     if (s > smax) s = smax;
@@ -812,191 +826,53 @@ static int splits_for_256(int64_t tiles, int ktiles) {
     return (ktiles + kps - 1) / kps;
 }
 
-int linear_fwd_splits_256(int M, int64_t K, int J) {
-    return splits_for_256((int64_t)((M + T - 1) / T) * ((J + T - 1) / T), (int)(K / BKH));
+// y_slabs[split][M][J] (fp32) = partial sums of x . w^T over the split's K range; the caller reduces + epilogue
+int launch_linear_fwd_256(const char* name, int parts, bool f16, const __hip_bfloat16* x, int64_t ldx, const __hip_bfloat16* w, int M, int64_t K,
+                          int J, float* slabs, int nsplit, hipStream_t st) {
+    return with_operands(parts, f16, [&](auto S, auto F16) {
+        typedef KCA256<S.NSEG> AL;
+        typedef KCB256<S.NSEG> BL;
+        const int64_t tiles_m = (M + T - 1) / T, tiles_n = (J + T - 1) / T;
+        const int ktiles = (int)(S.KSEG * K / BKH);
+        const int kps = (ktiles + nsplit - 1) / nsplit;
+        typename AL::P ap{x, ldx, M, 0, (int)K, S.A};
+        typename BL::P bp{w, S.PARTS * K, J, 0, (int)K, S.B};
+        return launch_256_t<AL, BL, 3, F16.value>(name, ap, bp, epi_slabs(slabs, M, J), tiles_m, tiles_n, nsplit, 1, ktiles, kps, st);
+    });
 }
 
-// y_slabs[split][M][J] (fp32) = partial sums of x[M][K] . w[J][K]^T over the split's K range; the caller reduces + epilogue
-int launch_linear_fwd_bf16_256(const char* name, const __hip_bfloat16* x, int64_t ldx, const __hip_bfloat16* w, int M, int64_t K,
-                               int J, float* slabs, int nsplit, bool f16, hipStream_t st) {
-    typedef KCLoader256<64> AL;
-    typedef KCLoader256<32> BL;
-    const int64_t tiles_m = (M + T - 1) / T, tiles_n = (J + T - 1) / T;
-    const int ktiles = (int)(K / BKH);
-    const int kps = (ktiles + nsplit - 1) / nsplit;
-    AL::P ap{x, ldx, M, 0, 0, 0u};
-    BL::P bp{w, K, J, 0, 0, 0u};
-    EpiP ep{EPI_RAW, slabs, J, M, J, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)M * J};
-    return launch_256<AL, BL, 3>(name, ap, bp, ep, tiles_m, tiles_n, nsplit, 1, ktiles, kps, f16, st);
+// dx[M][K] (fp32, or 16-bit into dx16: plain operands only) = dy . w: A K-contiguous (reduction index j), B row-contiguous; no split
+int launch_linear_dx_256(const char* name, int parts, bool f16, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* w, int M, int64_t K,
+                         int J, float* dx, __hip_bfloat16* dx16, int64_t lddx, const int* oscale, hipStream_t st) {
+    return with_operands(parts, f16, [&](auto S, auto F16) {
+        typedef KCA256<S.NSEG> AL;
+        typedef MCLoader256T<S.NSEG> BL;
+        const int64_t tiles_m = (M + T - 1) / T, tiles_n = (K + T - 1) / T;
+        const int ktiles = S.KSEG * J / BKH;
+        typename AL::P ap{dy, lddy, M, 0, J, S.A};
+        typename BL::P bp{w, S.PARTS * K, (int)K, J, 1, (int)K, S.B};
+        EpiP ep = epi_raw(dx, lddx, M, (int)K);
+        ep.out16 = dx16;
+        ep.oscale = oscale;
+        return launch_256_t<AL, BL, 4, F16.value>(name, ap, bp, ep, tiles_m, tiles_n, 1, 1, ktiles, ktiles, st);
+    });
 }
 
-// dx[M][K] (fp32, or 16-bit into dx16) = dy[M][J] . w[J][K]: A K-contiguous (reduction index j), B row-contiguous; no split
-int launch_linear_dx_bf16_256(const char* name, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* w, int M, int64_t K,
-                              int J, float* dx, __hip_bfloat16* dx16, int64_t lddx, bool f16, hipStream_t st) {
-    typedef KCLoader256<64> AL;
-    typedef MCLoader256 BL;
-    const int64_t tiles_m = (M + T - 1) / T, tiles_n = (K + T - 1) / T;
-    AL::P ap{dy, lddy, M, 0, 0, 0u};
-    BL::P bp{w, K, (int)K, J, 0, 0, 0u};
-    EpiP ep{EPI_RAW, dx, lddx, M, (int)K, nullptr, 0, nullptr, 0, nullptr, 0, 0, dx16};
-    return launch_256<AL, BL, 4>(name, ap, bp, ep, tiles_m, tiles_n, 1, 1, J / BKH, J / BKH, f16, st);
-}
-
-// dw[J][K] (fp32) = dy[M][J]^T . x[M][K]: both operands row-contiguous (the reduction index m is the slow one), no split:
-// a short reduction (M / 64 K-tiles) into a huge output — the 256^2 tile quarters the operand traffic per output byte
-int launch_linear_dw_bf16_256(const char* name, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* x, int64_t ldx, int M,
-                              int64_t K, int J, float* dw, bool f16, hipStream_t st) {
-    typedef MCLoader256 AL;
-    typedef MCLoader256 BL;
-    const int64_t tiles_m = (J + T - 1) / T, tiles_n = (K + T - 1) / T;
-    const int ktiles = (M + BKH - 1) / BKH;
-    AL::P ap{dy, lddy, J, M, 0, 0, 0u};
-    BL::P bp{x, ldx, (int)K, M, 0, 0, 0u};
-    EpiP ep{EPI_RAW, dw, K, J, (int)K, nullptr, 0, nullptr, 0, nullptr, 0, 0};
-    return launch_256<AL, BL, 5>(name, ap, bp, ep, tiles_m, tiles_n, 1, 1, ktiles, ktiles, f16, st);
-}
-
-// conv 3x3 weight gradient on the zero-padded pixel grid: slabs[split][Cout][9*Cin] (fp32), reduced by the caller
-int launch_wgrad_bf16_256(const char* name, const __hip_bfloat16* x_pad, const __hip_bfloat16* dy_pad, int Wp2, int Cin, int Cout,
-                          int64_t Mp, float* slabs, int nsplit, bool f16, hipStream_t st) {
-    typedef MCLoader256 AL;
-    typedef ConvWgradBLoader256 BL;
-    const int64_t tiles_m = (Cout + T - 1) / T, tiles_n = (9 * Cin + T - 1) / T;
-    const int ktiles = (int)((Mp + BKH - 1) / BKH);
-    GN_REQUIRE(nsplit >= 1 && nsplit <= 65535, GOALNET_E_SHAPE, "%s: bad split count %d", name, nsplit);
-    const int kps = (ktiles + nsplit - 1) / nsplit;
-    AL::P ap{dy_pad, Cout, Cout, Mp, 0, 0, 0u};
-    BL::P bp{x_pad, Wp2, Cin, Mp, Cin, 0, 0u};
-    EpiP ep{EPI_RAW, slabs, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)Cout * 9 * Cin};
-    return launch_256<AL, BL, 2>(name, ap, bp, ep, tiles_m, tiles_n, nsplit, 1, ktiles, kps, f16, st);
-}
-
-// ---- split operands: the same kernels over NSEG K-segments of [hi | mid | lo] (bf16x6: 3 parts, 6 segments) or [hi | mid]
-// (fp16x3: 2 parts of the power-of-two-scaled value, 3 segments, ep.oscale) operands (comment at SEGMAP_A) ----------------------
-template <int NSEG> struct SegCfg;
-template <> struct SegCfg<6> { static constexpr int PARTS = 3; static constexpr unsigned A = SEGMAP_A, B = SEGMAP_B; static constexpr bool F16 = false; };
-template <> struct SegCfg<3> { static constexpr int PARTS = 2; static constexpr unsigned A = SEGMAP_A3, B = SEGMAP_B3; static constexpr bool F16 = true; };
-
-// conv 3x3 forward / data gradient: x_pads = zero-padded [pixels][PARTS Cin], ws = [Cout][9][PARTS Cin]; fp32 result
-template <int NSEG>
-static int launch_conv_split_t(const char* name, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M, const __hip_bfloat16* ws,
-                               int Cout, const EpiP& ep, hipStream_t st) {
-    typedef ConvAPadLoader256<64, NSEG> AL;
-    typedef KCLoader256<32, NSEG> BL;
-    typedef SegCfg<NSEG> S;
-    const int64_t tiles_m = (M + T - 1) / T, tiles_n = (Cout + T - 1) / T;
-    typename AL::P ap{x_pads, H, W, S::PARTS * Cin, M, Cin, S::A};
-    typename BL::P bp{ws, (int64_t)9 * S::PARTS * Cin, Cout, S::PARTS * Cin, Cin, S::B};
-    const int kt = 9 * NSEG * Cin / BKH;
-    return ep.mode == EPI_BIAS_RELU && (ep.relu || ep.bias)
-        ? launch_256_t<AL, BL, 0, S::F16>(name, ap, bp, ep, tiles_m, tiles_n, 1, 0, kt, kt, st)
-        : launch_256_t<AL, BL, 1, S::F16>(name, ap, bp, ep, tiles_m, tiles_n, 1, 0, kt, kt, st);
-}
-int launch_conv_split_256(const char* name, int parts, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M,
-                          const __hip_bfloat16* ws, int Cout, const EpiP& ep, hipStream_t st) {
-    return parts == 3 ? launch_conv_split_t<6>(name, x_pads, H, W, Cin, M, ws, Cout, ep, st)
-                      : launch_conv_split_t<3>(name, x_pads, H, W, Cin, M, ws, Cout, ep, st);
-}
-
-int wgrad_split_splits_256(int parts, int64_t Mp, int Cin, int Cout) {
-    const int nseg = parts == 3 ? 6 : 3;
-    const int64_t tiles = (int64_t)((Cout + T - 1) / T) * ((9 * Cin + T - 1) / T);
-    const int ktiles = nseg * (int)((Mp + BKH - 1) / BKH);
-    int64_t s = (2048 + tiles - 1) / tiles;
-    const int64_t smax = ktiles / 64 > 1 ? ktiles / 64 : 1;
-    if (s > smax) s = smax;
-    for (int64_t c = s; c < s + 32 && c <= smax; ++c)
-        if ((tiles * c) % 256 == 0) { s = c; break; }
-    if (s > 1024) s = 1024;
-    const int kps = (int)((ktiles + s - 1) / s);
-    return (ktiles + kps - 1) / kps;
-}
-
-// conv 3x3 weight gradient: dy_pads = [padded pixels][PARTS Cout], x_pads = [padded pixels][PARTS Cin]; slabs[split][Cout][9 Cin]
-template <int NSEG>
-static int launch_wgrad_split_t(const char* name, const __hip_bfloat16* x_pads, const __hip_bfloat16* dy_pads, int Wp2, int Cin, int Cout,
-                                int64_t Mp, float* slabs, int nsplit, hipStream_t st) {
-    typedef MCLoader256T<NSEG> AL;
-    typedef ConvWgradBLoader256T<NSEG> BL;
-    typedef SegCfg<NSEG> S;
-    const int64_t tiles_m = (Cout + T - 1) / T, tiles_n = (9 * Cin + T - 1) / T;
-    const int seg_kt = (int)((Mp + BKH - 1) / BKH), ktiles = NSEG * seg_kt;
-    GN_REQUIRE(nsplit >= 1 && nsplit <= 65535, GOALNET_E_SHAPE, "%s: bad split count %d", name, nsplit);
-    const int kps = (ktiles + nsplit - 1) / nsplit;
-    typename AL::P ap{dy_pads, (int64_t)S::PARTS * Cout, Cout, Mp, seg_kt, Cout, S::A};
-    typename BL::P bp{x_pads, Wp2, Cin, Mp, S::PARTS * Cin, seg_kt, S::B};
-    EpiP ep{EPI_RAW, slabs, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)Cout * 9 * Cin};
-    return launch_256_t<AL, BL, 2, S::F16>(name, ap, bp, ep, tiles_m, tiles_n, nsplit, 1, ktiles, kps, st);
-}
-int launch_wgrad_split_256(const char* name, int parts, const __hip_bfloat16* x_pads, const __hip_bfloat16* dy_pads, int Wp2, int Cin,
-                           int Cout, int64_t Mp, float* slabs, int nsplit, hipStream_t st) {
-    return parts == 3 ? launch_wgrad_split_t<6>(name, x_pads, dy_pads, Wp2, Cin, Cout, Mp, slabs, nsplit, st)
-                      : launch_wgrad_split_t<3>(name, x_pads, dy_pads, Wp2, Cin, Cout, Mp, slabs, nsplit, st);
-}
-
-// linear5 on split operands: xs [M][PARTS K], ws [J][PARTS K], dys [M][PARTS J] (parts side by side along the row)
-int linear_fwd_split_splits_256(int parts, int M, int64_t K, int J) {
-    return splits_for_256((int64_t)((M + T - 1) / T) * ((J + T - 1) / T), (int)((parts == 3 ? 6 : 3) * K / BKH));
-}
-
-template <int NSEG>
-static int launch_linear_fwd_split_t(const char* name, const __hip_bfloat16* xs, const __hip_bfloat16* ws, int M, int64_t K, int J,
-                                     float* slabs, int nsplit, hipStream_t st) {
-    typedef KCLoader256<64, NSEG> AL;
-    typedef KCLoader256<32, NSEG> BL;
-    typedef SegCfg<NSEG> S;
-    const int64_t tiles_m = (M + T - 1) / T, tiles_n = (J + T - 1) / T;
-    const int ktiles = (int)(NSEG * K / BKH);
-    const int kps = (ktiles + nsplit - 1) / nsplit;
-    typename AL::P ap{xs, S::PARTS * K, M, 0, (int)K, S::A};
-    typename BL::P bp{ws, S::PARTS * K, J, 0, (int)K, S::B};
-    EpiP ep{EPI_RAW, slabs, J, M, J, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)M * J};
-    return launch_256_t<AL, BL, 3, S::F16>(name, ap, bp, ep, tiles_m, tiles_n, nsplit, 1, ktiles, kps, st);
-}
-int launch_linear_fwd_split_256(const char* name, int parts, const __hip_bfloat16* xs, const __hip_bfloat16* ws, int M, int64_t K, int J,
-                                float* slabs, int nsplit, hipStream_t st) {
-    return parts == 3 ? launch_linear_fwd_split_t<6>(name, xs, ws, M, K, J, slabs, nsplit, st)
-                      : launch_linear_fwd_split_t<3>(name, xs, ws, M, K, J, slabs, nsplit, st);
-}
-
-template <int NSEG>
-static int launch_linear_dx_split_t(const char* name, const __hip_bfloat16* dys, const __hip_bfloat16* ws, int M, int64_t K, int J, float* dx,
-                                    int64_t lddx, const int* oscale, hipStream_t st) {
-    typedef KCLoader256<64, NSEG> AL;
-    typedef MCLoader256T<NSEG> BL;
-    typedef SegCfg<NSEG> S;
-    const int64_t tiles_m = (M + T - 1) / T, tiles_n = (K + T - 1) / T;
-    const int ktiles = NSEG * J / BKH;
-    typename AL::P ap{dys, (int64_t)S::PARTS * J, M, 0, J, S::A};
-    typename BL::P bp{ws, S::PARTS * K, (int)K, J, 1, (int)K, S::B};
-    EpiP ep{EPI_RAW, dx, lddx, M, (int)K, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr};
-    ep.oscale = oscale;
-    return launch_256_t<AL, BL, 4, S::F16>(name, ap, bp, ep, tiles_m, tiles_n, 1, 1, ktiles, ktiles, st);
-}
-int launch_linear_dx_split_256(const char* name, int parts, const __hip_bfloat16* dys, const __hip_bfloat16* ws, int M, int64_t K, int J,
-                               float* dx, int64_t lddx, const int* oscale, hipStream_t st) {
-    return parts == 3 ? launch_linear_dx_split_t<6>(name, dys, ws, M, K, J, dx, lddx, oscale, st)
-                      : launch_linear_dx_split_t<3>(name, dys, ws, M, K, J, dx, lddx, oscale, st);
-}
-
-template <int NSEG>
-static int launch_linear_dw_split_t(const char* name, const __hip_bfloat16* dys, const __hip_bfloat16* xs, int M, int64_t K, int J, float* dw,
-                                    const int* oscale, hipStream_t st) {
-    typedef MCLoader256T<NSEG> AL;
-    typedef MCLoader256T<NSEG> BL;
-    typedef SegCfg<NSEG> S;
-    const int64_t tiles_m = (J + T - 1) / T, tiles_n = (K + T - 1) / T;
-    const int ktiles = NSEG * ((M + BKH - 1) / BKH);
-    typename AL::P ap{dys, (int64_t)S::PARTS * J, J, M, 1, J, S::A};
-    typename BL::P bp{xs, S::PARTS * K, (int)K, M, 1, (int)K, S::B};
-    EpiP ep{EPI_RAW, dw, K, J, (int)K, nullptr, 0, nullptr, 0, nullptr, 0, 0};
-    ep.oscale = oscale;
-    return launch_256_t<AL, BL, 5, S::F16>(name, ap, bp, ep, tiles_m, tiles_n, 1, 1, ktiles, ktiles, st);
-}
-int launch_linear_dw_split_256(const char* name, int parts, const __hip_bfloat16* dys, const __hip_bfloat16* xs, int M, int64_t K, int J,
-                               float* dw, const int* oscale, hipStream_t st) {
-    return parts == 3 ? launch_linear_dw_split_t<6>(name, dys, xs, M, K, J, dw, oscale, st)
-                      : launch_linear_dw_split_t<3>(name, dys, xs, M, K, J, dw, oscale, st);
+// dw[J][K] (fp32) = dy^T . x: both operands row-contiguous (the reduction index m is the slow one), no split: a short
+// reduction (M / 64 K-tiles per segment) into a huge output — the 256^2 tile quarters the operand traffic per output byte
+int launch_linear_dw_256(const char* name, int parts, bool f16, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* x, int64_t ldx,
+                         int M, int64_t K, int J, float* dw, const int* oscale, hipStream_t st) {
+    return with_operands(parts, f16, [&](auto S, auto F16) {
+        typedef MCLoader256T<S.NSEG> AL;
+        typedef MCLoader256T<S.NSEG> BL;
+        const int64_t tiles_m = (J + T - 1) / T, tiles_n = (K + T - 1) / T;
+        const int ktiles = S.KSEG * ((M + BKH - 1) / BKH);
+        typename AL::P ap{dy, lddy, J, M, 1, J, S.A};
+        typename BL::P bp{x, ldx, (int)K, M, 1, (int)K, S.B};
+        EpiP ep = epi_raw(dw, K, J, (int)K);
+        ep.oscale = oscale;
+        return launch_256_t<AL, BL, 5, F16.value>(name, ap, bp, ep, tiles_m, tiles_n, 1, 1, ktiles, ktiles, st);
+    });
 }
 
 }  // namespace goalnet

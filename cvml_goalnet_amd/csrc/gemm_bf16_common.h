@@ -61,21 +61,26 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds_dst, u
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds_dst, 16, (int)voff, (int)soff, 0, 0);
 }
 
-// implemented in gemm_bf16_256.hip: conv 3x3 on zero-padded bf16 activations with the 256 x 256 phased tile
-// (f16: the operands / the 16-bit output are IEEE fp16 instead of bf16)
-int launch_conv_bf16_256(const char* name, const __hip_bfloat16* x_pad, int H, int W, int Cin, int64_t M, const __hip_bfloat16* w,
-                         int Cout, const EpiP& ep, bool f16, hipStream_t st);
-
+// ---- the launch layer of the 256 x 256 phased tile (gemm_bf16_256.hip): one launcher per contraction. parts = 1: plain 16-bit
+// operands, f16 says whether they (and a 16-bit result) are IEEE fp16 instead of bf16; parts = 3: bf16 triples, parts = 2: scaled
+// fp16 pairs (csrc/split3.hip; f16 is ignored, the format follows from parts). Operand rows hold their parts side by side.
+int launch_conv_256(const char* name, int parts, bool f16, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M,
+                    const __hip_bfloat16* ws, int Cout, const EpiP& ep, hipStream_t st);
+int launch_wgrad_256(const char* name, int parts, bool f16, const __hip_bfloat16* x_pads, const __hip_bfloat16* dy_pads, int Wp2, int Cin,
+                     int Cout, int64_t Mp, float* slabs, int nsplit, hipStream_t st);
+int launch_linear_fwd_256(const char* name, int parts, bool f16, const __hip_bfloat16* x, int64_t ldx, const __hip_bfloat16* w, int M, int64_t K,
+                          int J, float* slabs, int nsplit, hipStream_t st);
+int launch_linear_dx_256(const char* name, int parts, bool f16, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* w, int M, int64_t K,
+                         int J, float* dx, __hip_bfloat16* dx16, int64_t lddx, const int* oscale, hipStream_t st);
+int launch_linear_dw_256(const char* name, int parts, bool f16, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* x, int64_t ldx,
+                         int M, int64_t K, int J, float* dw, const int* oscale, hipStream_t st);
+// split counts of the two split-K roles (the slabs the caller lends and reduces)
+int wgrad_splits_256(int parts, int64_t Mp, int Cin, int Cout);
+int linear_fwd_splits_256(int parts, int M, int64_t K, int J);
 const char* conv_bf16_256_kernel_name(int role);
-int wgrad_splits_256(int64_t Mp, int Cin, int Cout);
-int linear_fwd_splits_256(int M, int64_t K, int J);
-int launch_linear_fwd_bf16_256(const char* name, const __hip_bfloat16* x, int64_t ldx, const __hip_bfloat16* w, int M, int64_t K,
-                               int J, float* slabs, int nsplit, bool f16, hipStream_t st);
-int launch_linear_dx_bf16_256(const char* name, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* w, int M, int64_t K,
-                              int J, float* dx, __hip_bfloat16* dx16, int64_t lddx, bool f16, hipStream_t st);
-int launch_linear_dw_bf16_256(const char* name, const __hip_bfloat16* dy, int64_t lddy, const __hip_bfloat16* x, int64_t ldx, int M,
-                              int64_t K, int J, float* dw, bool f16, hipStream_t st);
-int launch_wgrad_bf16_256(const char* name, const __hip_bfloat16* x_pad, const __hip_bfloat16* dy_pad, int Wp2, int Cin, int Cout,
-                          int64_t Mp, float* slabs, int nsplit, bool f16, hipStream_t st);
+
+// implemented in gemm_bf16.hip: conv 3x3 on split operands with <= 64 output channels, 128 x 64 tile
+int launch_conv_split_h64(const char* name, int parts, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M,
+                          const __hip_bfloat16* ws, int Cout, const EpiP& ep, hipStream_t st);
 
 }  // namespace goalnet

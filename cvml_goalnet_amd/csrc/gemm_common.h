@@ -40,6 +40,37 @@ struct EpiP {
     const int* oscale = nullptr;
 };
 
+// Host-side makers, one per epilogue shape in use: a call site names what it sets, everything else is off (0 / null). What few
+// sites add on top (out16, oscale, corr_*, slabs + tile_ctr) they assign by name.
+// raw accumulators to out[rows][ld]
+inline EpiP epi_raw(float* out, int64_t ld, int rows, int cols) {
+    EpiP e{};
+    e.mode = EPI_RAW; e.out = out; e.ld = ld; e.rows = rows; e.cols = cols;
+    return e;
+}
+// raw split-K partial sums: split s to slabs + s * rows * cols, dense rows (ld = cols)
+inline EpiP epi_slabs(float* slabs, int rows, int cols) {
+    EpiP e = epi_raw(slabs, cols, rows, cols);
+    e.slab_stride = (int64_t)rows * cols;
+    return e;
+}
+// act(v + bias) with bias nullable and relu 0 / 1; with a multiplier `mul` (dropout mask) and / or a saved multiplier `mult_out`
+// the general per-element form (EPI_FULL)
+inline EpiP epi_act(float* out, int64_t ld, int rows, int cols, const float* bias, int relu, const float* mul = nullptr,
+                    int64_t ldmul = 0, float* mult_out = nullptr, int64_t ldmo = 0) {
+    EpiP e = epi_raw(out, ld, rows, cols);
+    e.mode = (mul || mult_out) ? EPI_FULL : EPI_BIAS_RELU;
+    e.bias = bias; e.relu = relu; e.mul = mul; e.ldmul = ldmul; e.mult_out = mult_out; e.ldmo = ldmo;
+    return e;
+}
+// v * mul[row][col]; mul null: raw
+inline EpiP epi_mul(float* out, int64_t ld, int rows, int cols, const float* mul, int64_t ldmul) {
+    EpiP e = epi_raw(out, ld, rows, cols);
+    e.mode = mul ? EPI_MUL : EPI_RAW;
+    e.mul = mul; e.ldmul = ldmul;
+    return e;
+}
+
 __device__ __forceinline__ float epi_apply(const EpiP& e, float v, int64_t row, int col) {
     if (e.bias) v += e.bias[col];
     float g = 1.f;

@@ -1268,7 +1268,7 @@ int goalnet_conv3x3_fwd(const float* x, const float* scale, const float* shift, 
     GN_REQUIRE(M < (1ll << 31) - 256, GOALNET_E_SHAPE, "conv3x3_fwd: N*H*W too large");
     hipStream_t st = (hipStream_t)stream;
     KCLoader<false>::P bp{w, (int64_t)9 * Cin, Cout, nullptr, nullptr, 1, Cin};
-    const EpiP efinal{EPI_BIAS_RELU, y, Cout, (int)M, Cout, bias, relu, nullptr, 0, nullptr, 0, 0};
+    const EpiP efinal = epi_act(y, Cout, (int)M, Cout, bias, relu);
     EpiP ep = efinal;
     const int ktiles = 9 * Cin / BK;
     // split K only when the caller supplied the workspace goalnet_conv3x3_fwd_ws_bytes asks for
@@ -1276,7 +1276,7 @@ int goalnet_conv3x3_fwd(const float* x, const float* scale, const float* shift, 
     if (nsplit > 1) {
         GN_REQUIRE(aligned16(ws) && ws_bytes >= goalnet_conv3x3_fwd_ws_bytes(N, H, W, Cin, Cout), GOALNET_E_WORKSPACE,
                    "conv3x3_fwd: workspace too small or misaligned");
-        ep = EpiP{EPI_RAW, (float*)ws, Cout, (int)M, Cout, nullptr, 0, nullptr, 0, nullptr, 0, M * Cout};
+        ep = epi_slabs((float*)ws, (int)M, Cout);
     }
     const bool narrow = Cout <= 64 && !getenv("GOALNET_F32_N64_OFF");       // 128 x 64 tile (conv2's data gradient: 256 -> 64 channels)
     // the caller lent zeroed ticket counters, one per output tile: the last block of each tile reduces (no second launch)
@@ -1419,13 +1419,13 @@ int goalnet_conv3x3_wgrad(const float* x, const float* scale, const float* shift
         GN_LAUNCH_CHECK("conv3x3_wgrad.border_u");
     }
     MCLoader<false>::P ap{dy, Cout, Cout, (int)M, nullptr, nullptr, 1};
-    EpiP ep{EPI_RAW, slabs, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, slab};
+    EpiP ep = epi_slabs(slabs, Cout, 9 * Cin);
     // few frames (no rank-one correction to apply): with ticket counters lent by the caller the last block of each tile reduces
     const bool fused = nsplit > 1 && tile_ctr && (dsel || !scale) &&
                        (int64_t)n_ctr >= (int64_t)((Cout + BM - 1) / BM) * ((9 * Cin + BN - 1) / BN);
     if (fused) {
-        ep = EpiP{EPI_RAW, dw, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, slab};
-        ep.slabs = slabs; ep.tile_ctr = tile_ctr;
+        ep = epi_raw(dw, (int64_t)9 * Cin, Cout, 9 * Cin);
+        ep.slabs = slabs; ep.slab_stride = slab; ep.tile_ctr = tile_ctr;
     }
     int rc;
     if (scale && dsel) {
@@ -1439,7 +1439,7 @@ int goalnet_conv3x3_wgrad(const float* x, const float* scale, const float* shift
         rc = launch_gemm<MCLoader<false>, ConvWgradBLoader<false>>("conv3x3_wgrad", ap, bp, ep, Cout, 9 * Cin, ktiles, nsplit, 1, st);
     }
     if (rc || fused) return rc;
-    EpiP er{EPI_RAW, dw, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, 0};
+    EpiP er = epi_raw(dw, (int64_t)9 * Cin, Cout, 9 * Cin);
     if (scale && !dsel) { er.corr_u = bu; er.corr_sh = shift; er.corr_C = Cin; }
     return launch_splitk_reduce("conv3x3_wgrad.reduce", slabs, nsplit, slab, er, st);
 }
@@ -1469,7 +1469,7 @@ int goalnet_linear_fwd(const float* x, int64_t ldx, const float* scale, const fl
     GN_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(scale) && aligned16(shift) && ldx % 4 == 0 && ldy % 4 == 0,
                GOALNET_E_ALIGN, "linear_fwd: pointers / leading dims must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    EpiP efinal{(dropmask || mult_out) ? EPI_FULL : EPI_BIAS_RELU, y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult, 0};
+    const EpiP efinal = epi_act(y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult);
     if (M <= SKINNY_MAX_M) {          // the reference's 10-frame sub-batches: weight-streaming kernels (skinny.hip)
         const size_t need = skinny_fwd_ws_bytes(M, K, J);
         GN_REQUIRE(need == 0 || (ws && aligned16(ws) && ws_bytes >= need), GOALNET_E_WORKSPACE, "linear_fwd: workspace too small");
@@ -1482,7 +1482,7 @@ int goalnet_linear_fwd(const float* x, int64_t ldx, const float* scale, const fl
     if (nsplit > 1) {
         GN_REQUIRE(ws && aligned16(ws), GOALNET_E_WORKSPACE, "linear_fwd: split-K needs a 16-byte aligned workspace");
         GN_REQUIRE(ws_bytes >= goalnet_linear_fwd_ws_bytes(M, K, J), GOALNET_E_WORKSPACE, "linear_fwd: workspace too small");
-        ep = EpiP{EPI_RAW, (float*)ws, J, M, J, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)M * J};
+        ep = epi_slabs((float*)ws, M, J);
     }
     int rc;
     if (scale) {
@@ -1509,7 +1509,7 @@ int goalnet_linear_bwd_dx(const float* dy, int64_t lddy, const float* w, const f
         return skinny_linear_dx(dy, lddy, w, mult, ldmult, dx, lddx, M, K, J, st);
     KCLoader<false>::P ap{dy, lddy, M, nullptr, nullptr, 1, 0};
     MCLoader<false>::P bp{w, K, (int)K, J, nullptr, nullptr, 1};
-    EpiP ep{mult ? EPI_MUL : EPI_RAW, dx, lddx, M, (int)K, nullptr, 0, mult, ldmult, nullptr, 0, 0};
+    const EpiP ep = epi_mul(dx, lddx, M, (int)K, mult, ldmult);
     return launch_gemm<KCLoader<false>, MCLoader<false>>("linear_bwd_dx", ap, bp, ep, M, K, J / BK, 1, 1, st);
 }
 
@@ -1528,7 +1528,7 @@ int goalnet_linear_bwd_dw(const float* dy, int64_t lddy, const float* x, int64_t
     if (db) { const int rc = goalnet_colsum(dy, lddy, M, J, db, stream); if (rc) return rc; }
     const int ktiles = (M + BK - 1) / BK;
     MCLoader<false>::P ap{dy, lddy, J, M, nullptr, nullptr, 1};
-    EpiP ep{EPI_RAW, dw, K, J, (int)K, nullptr, 0, nullptr, 0, nullptr, 0, 0};
+    const EpiP ep = epi_raw(dw, K, J, (int)K);
     if (scale) {
         MCLoader<true>::P bp{x, ldx, (int)K, M, scale, shift, bnC};
         return launch_gemm<MCLoader<false>, MCLoader<true>>("linear_bwd_dw", ap, bp, ep, J, K, ktiles, 1, 1, st);

@@ -231,7 +231,7 @@ int skinny_linear_fwd(const float* x, int64_t ldx, const float* scale, const flo
                       const EpiP& efinal, int M, int64_t K, int J, void* ws, hipStream_t st) {
     const int KS = skinny_fwd_splits(K);
     EpiP ep = efinal;
-    if (KS > 1) ep = EpiP{EPI_RAW, (float*)ws, J, M, J, nullptr, 0, nullptr, 0, nullptr, 0, (int64_t)M * J};
+    if (KS > 1) ep = epi_slabs((float*)ws, M, J);
     if (KS >= 8) {
         const dim3 grid((unsigned)((J + 15) / 16), (unsigned)KS);
         SKINNY_DISPATCH(M, hipLaunchKernelGGL((skinny_fwd_kernel<MR, 4, 1>), grid, dim3(256), 0, st, x, ldx, scale, shift, bnC, w, ep, M, K, J, KS));

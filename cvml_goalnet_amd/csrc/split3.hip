@@ -24,23 +24,6 @@
 
 using namespace goalnet;
 
-namespace goalnet {
-int launch_conv_split_256(const char* name, int parts, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M,
-                          const __hip_bfloat16* ws, int Cout, const EpiP& ep, hipStream_t st);
-int launch_conv_split_h64(const char* name, int parts, const __hip_bfloat16* x_pads, int H, int W, int Cin, int64_t M,
-                          const __hip_bfloat16* ws, int Cout, const EpiP& ep, hipStream_t st);
-int wgrad_split_splits_256(int parts, int64_t Mp, int Cin, int Cout);
-int launch_wgrad_split_256(const char* name, int parts, const __hip_bfloat16* x_pads, const __hip_bfloat16* dy_pads, int Wp2, int Cin,
-                           int Cout, int64_t Mp, float* slabs, int nsplit, hipStream_t st);
-int linear_fwd_split_splits_256(int parts, int M, int64_t K, int J);
-int launch_linear_fwd_split_256(const char* name, int parts, const __hip_bfloat16* xs, const __hip_bfloat16* ws, int M, int64_t K, int J,
-                                float* slabs, int nsplit, hipStream_t st);
-int launch_linear_dx_split_256(const char* name, int parts, const __hip_bfloat16* dys, const __hip_bfloat16* ws, int M, int64_t K, int J,
-                               float* dx, int64_t lddx, const int* oscale, hipStream_t st);
-int launch_linear_dw_split_256(const char* name, int parts, const __hip_bfloat16* dys, const __hip_bfloat16* xs, int M, int64_t K, int J,
-                               float* dw, const int* oscale, hipStream_t st);
-}  // namespace goalnet
-
 namespace {
 
 __device__ __forceinline__ float bf16_part(float v, unsigned short& bits) {
@@ -269,19 +252,19 @@ int goalnet_conv3x3_fwd_split(int parts, const void* x_pads, const void* ws, con
     // byte offsets inside one tile's window of the padded tensor are 32-bit (ConvAPadLoader256)
     GN_REQUIRE((int64_t)(256 + 4 * (W + 2) + 2 * (int64_t)(H + 2) * (W + 2)) * parts * Cin * 2 < (1ll << 32) - 4096, GOALNET_E_SHAPE,
                "conv3x3_fwd_split: frame too large for one tile window");
-    EpiP ep{EPI_BIAS_RELU, y, Cout, (int)M, Cout, bias, relu, nullptr, 0, nullptr, 0, 0};
+    EpiP ep = epi_act(y, Cout, (int)M, Cout, bias, relu);
     ep.oscale = parts == 2 ? oscale : nullptr;
     // <= 64 output channels (a data gradient into 64 channels): the 128 x 64 tile; a 256-wide tile would be three quarters empty
     if (Cout <= 64) return launch_conv_split_h64("conv3x3_fwd_split(128x64)", parts, (const __hip_bfloat16*)x_pads, H, W, Cin, M,
                                                  (const __hip_bfloat16*)ws, Cout, ep, (hipStream_t)stream);
-    return launch_conv_split_256("conv3x3_fwd_split", parts, (const __hip_bfloat16*)x_pads, H, W, Cin, M, (const __hip_bfloat16*)ws, Cout, ep,
-                                 (hipStream_t)stream);
+    return launch_conv_256("conv3x3_fwd_split", parts, false, (const __hip_bfloat16*)x_pads, H, W, Cin, M, (const __hip_bfloat16*)ws, Cout, ep,
+                           (hipStream_t)stream);
 }
 
 size_t goalnet_conv3x3_wgrad_split_ws_bytes(int parts, int N, int H, int W, int Cin, int Cout) {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (parts != 2 && parts != 3)) return 0;
     const int64_t Mp = (int64_t)N * (H + 2) * (W + 2);
-    return (size_t)wgrad_split_splits_256(parts, Mp, Cin, Cout) * (size_t)Cout * 9 * Cin * sizeof(float);
+    return (size_t)wgrad_splits_256(parts, Mp, Cin, Cout) * (size_t)Cout * 9 * Cin * sizeof(float);
 }
 
 /* dw[Cout][3][3][Cin] (fp32) = sum over the padded pixel grid of dy[pm][co] * x[pm + shift(tap)][ci], both operands split:
@@ -298,11 +281,11 @@ int goalnet_conv3x3_wgrad_split(int parts, const void* x_pads, const void* dy_pa
     GN_REQUIRE(ws_bytes >= goalnet_conv3x3_wgrad_split_ws_bytes(parts, N, H, W, Cin, Cout), GOALNET_E_WORKSPACE, "conv3x3_wgrad_split: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int64_t slab = (int64_t)Cout * 9 * Cin;
-    const int ns = wgrad_split_splits_256(parts, Mp, Cin, Cout);
-    const int rc = launch_wgrad_split_256("conv3x3_wgrad_split", parts, (const __hip_bfloat16*)x_pads, (const __hip_bfloat16*)dy_pads, W + 2, Cin, Cout,
-                                          Mp, (float*)ws, ns, st);
+    const int ns = wgrad_splits_256(parts, Mp, Cin, Cout);
+    const int rc = launch_wgrad_256("conv3x3_wgrad_split", parts, false, (const __hip_bfloat16*)x_pads, (const __hip_bfloat16*)dy_pads, W + 2, Cin, Cout,
+                                    Mp, (float*)ws, ns, st);
     if (rc) return rc;
-    EpiP er{EPI_RAW, dw, (int64_t)9 * Cin, Cout, 9 * Cin, nullptr, 0, nullptr, 0, nullptr, 0, 0};
+    EpiP er = epi_raw(dw, (int64_t)9 * Cin, Cout, 9 * Cin);
     er.oscale = parts == 2 ? oscale : nullptr;
     return launch_splitk_reduce("conv3x3_wgrad_split.reduce", (const float*)ws, ns, slab, er, st);
 }
@@ -317,7 +300,7 @@ int goalnet_linear_split_ok(int parts, int M, int64_t K, int J) {
 
 size_t goalnet_linear_fwd_split_ws_bytes(int parts, int M, int64_t K, int J) {
     if (!goalnet_linear_split_ok(parts, M, K, J)) return 0;
-    return (size_t)linear_fwd_split_splits_256(parts, M, K, J) * (size_t)M * (size_t)J * sizeof(float);
+    return (size_t)linear_fwd_splits_256(parts, M, K, J) * (size_t)M * (size_t)J * sizeof(float);
 }
 
 int goalnet_linear_fwd_split(int parts, const void* xs, const void* wsp, const float* bias, int relu, const float* dropmask, int64_t ldmask,
@@ -329,10 +312,11 @@ int goalnet_linear_fwd_split(int parts, const void* xs, const void* wsp, const f
     GN_REQUIRE(aligned16(xs) && aligned16(wsp) && aligned16(y) && aligned16(ws), GOALNET_E_ALIGN, "linear_fwd_split: alignment");
     GN_REQUIRE(ws_bytes >= goalnet_linear_fwd_split_ws_bytes(parts, M, K, J), GOALNET_E_WORKSPACE, "linear_fwd_split: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const int ns = linear_fwd_split_splits_256(parts, M, K, J);
-    EpiP efin{(dropmask || mult_out) ? EPI_FULL : EPI_BIAS_RELU, y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult, 0};
+    const int ns = linear_fwd_splits_256(parts, M, K, J);
+    EpiP efin = epi_act(y, ldy, M, J, bias, relu, dropmask, ldmask, mult_out, ldmult);
     efin.oscale = parts == 2 ? oscale : nullptr;
-    const int rc = launch_linear_fwd_split_256("linear_fwd_split", parts, (const __hip_bfloat16*)xs, (const __hip_bfloat16*)wsp, M, K, J, (float*)ws, ns, st);
+    const int rc = launch_linear_fwd_256("linear_fwd_split", parts, false, (const __hip_bfloat16*)xs, parts * K, (const __hip_bfloat16*)wsp, M, K, J,
+                                         (float*)ws, ns, st);
     if (rc) return rc;
     return launch_splitk_reduce("linear_fwd_split.reduce", (const float*)ws, ns, (int64_t)M * J, efin, st);
 }
@@ -344,8 +328,8 @@ int goalnet_linear_bwd_dx_split(int parts, const void* dys, const void* wsp, flo
     GN_REQUIRE(goalnet_linear_split_ok(parts, M, K, J) && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dx_split: dims not served");
     GN_REQUIRE(lddx % 4 == 0, GOALNET_E_ALIGN, "linear_bwd_dx_split: lddx must be a multiple of 16 bytes");
     GN_REQUIRE(aligned16(dys) && aligned16(wsp) && aligned16(dx), GOALNET_E_ALIGN, "linear_bwd_dx_split: alignment");
-    return launch_linear_dx_split_256("linear_bwd_dx_split", parts, (const __hip_bfloat16*)dys, (const __hip_bfloat16*)wsp, M, K, J, dx, lddx,
-                                      parts == 2 ? oscale : nullptr, (hipStream_t)stream);
+    return launch_linear_dx_256("linear_bwd_dx_split", parts, false, (const __hip_bfloat16*)dys, (int64_t)parts * J, (const __hip_bfloat16*)wsp, M, K, J,
+                                dx, nullptr, lddx, parts == 2 ? oscale : nullptr, (hipStream_t)stream);
 }
 
 /* dw[j][k] (fp32) = sum_m dy[m][j] x[m][k] from dys [M][parts J] and xs [M][parts K] */
@@ -353,8 +337,8 @@ int goalnet_linear_bwd_dw_split(int parts, const void* dys, const void* xs, floa
     GN_REQUIRE(dys && xs && dw && (parts == 3 || oscale), GOALNET_E_NULL, "linear_bwd_dw_split: null pointer (parts = 2 needs oscale)");
     GN_REQUIRE(goalnet_linear_split_ok(parts, M, K, J) && K < (1ll << 31) - 256, GOALNET_E_SHAPE, "linear_bwd_dw_split: dims not served");
     GN_REQUIRE(aligned16(dys) && aligned16(xs) && aligned16(dw), GOALNET_E_ALIGN, "linear_bwd_dw_split: alignment");
-    return launch_linear_dw_split_256("linear_bwd_dw_split", parts, (const __hip_bfloat16*)dys, (const __hip_bfloat16*)xs, M, K, J, dw,
-                                      parts == 2 ? oscale : nullptr, (hipStream_t)stream);
+    return launch_linear_dw_256("linear_bwd_dw_split", parts, false, (const __hip_bfloat16*)dys, (int64_t)parts * J, (const __hip_bfloat16*)xs, parts * K,
+                                M, K, J, dw, parts == 2 ? oscale : nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
-"""Prints a hash of the 16-bit / fp32 outputs of the 256^2 phased tile (conv forward with bias + ReLU, data-gradient form
-without) on whole and ragged shapes: run under two builds (GOALNET_LIB_PATH) the lines must be identical, because the
-operand order of the MFMA changes neither the products nor the order of the K sum."""
+"""Prints a hash of the outputs of every contraction of the 256^2 phased tile on whole and ragged shapes: conv forward with bias +
+ReLU and the data-gradient form without (16-bit and fp32 results), weight gradient and linear5's forward / dX / dW, in bf16 and
+fp16, then the same on split operands (bf16 triples, scaled fp16 pairs). Run under two builds (GOALNET_LIB_PATH) the lines
+must be identical when only host code or the arrangement of the kernels changed: neither the products nor the order of the K
+sum may move (the MFMA operand order of the roles with a 16-bit result was settled with it)."""
 import hashlib
 import os
 import sys
@@ -77,22 +79,52 @@ for h16 in (torch.bfloat16, torch.float16):
         print(str(h16)[6:], "linear", M, K, J, *h(*out), float(dw.abs().max()), float(dx.abs().max()))
 
 
-# split operands (parts = 3: bf16 triples; parts = 2: scaled fp16 pairs, bias added after the unscaling from the per-tile LDS copy): three
-# column tiles, > 256 tiles, bias + ReLU
-for parts in (3, 2):
+# split operands (parts = 3: bf16 triples; parts = 2: scaled fp16 pairs, bias added after the unscaling from the per-tile LDS copy)
+def split_rows(parts, t, rows, C):
+    """(t as [rows][parts C] 16-bit, its magnitude word for parts = 2)"""
+    amax = ops.absmax(t, torch.zeros(1, dtype=torch.int32, device=dev), rows, C) if parts == 2 else None
     dt = torch.bfloat16 if parts == 3 else torch.float16
+    return ops.split_rows(parts, t, torch.empty(rows * parts * C, dtype=dt, device=dev), rows, C, amax=amax), amax
+
+
+def split_padded(parts, t, n, hh, ww, C):
+    amax = ops.absmax(t, torch.zeros(1, dtype=torch.int32, device=dev), n * hh * ww, C) if parts == 2 else None
+    _, tp = ops.padded_bf16_alloc(n, hh, ww, parts * C, dev, dtype=torch.bfloat16 if parts == 3 else torch.float16)
+    return ops.split_padded(parts, t, None, None, tp, n, hh, ww, C, amax=amax), amax
+
+
+def oscale(parts, a, b):
+    return ops.split_scales(a, b) if parts == 2 else None
+
+
+for parts in (3, 2):
+    # conv forward: three column tiles, > 256 tiles, bias + ReLU
     n, hh, ww, cin, cout = 8, 72, 72, 64, 768
     x = torch.randn(n, hh, ww, cin, device=dev)
     w = torch.randn(cout * 9 * cin, device=dev) * 0.05
     b = torch.randn(cout, device=dev)
-    ax = aw = osc = None
-    if parts == 2:
-        ax = ops.absmax(x, torch.zeros(1, dtype=torch.int32, device=dev), n * hh * ww, cin)
-        aw = ops.absmax(w, torch.zeros(1, dtype=torch.int32, device=dev), cout * 9, cin)
-        osc = ops.split_scales(ax, aw)
-    _, xp = ops.padded_bf16_alloc(n, hh, ww, parts * cin, dev, dtype=dt)
-    ops.split_padded(parts, x, None, None, xp, n, hh, ww, cin, amax=ax)
-    wsp = ops.split_rows(parts, w, torch.empty(cout * 9 * parts * cin, dtype=dt, device=dev), cout * 9, cin, amax=aw)
+    xp, ax = split_padded(parts, x, n, hh, ww, cin)
+    wsp, aw = split_rows(parts, w, cout * 9, cin)
     y = torch.full((n, hh, ww, cout), 7.0, device=dev)
-    ops.conv3x3_fwd_split(parts, xp, wsp, b, True, y, n, hh, ww, cin, cout, oscale=osc)
+    ops.conv3x3_fwd_split(parts, xp, wsp, b, True, y, n, hh, ww, cin, cout, oscale=oscale(parts, ax, aw))
     print("split", parts, n, hh, ww, cin, cout, *h(y), float(y.abs().max()))
+    # weight gradient, ragged pixel count
+    n, hh, ww, cin, cout = 3, 37, 29, 64, 256
+    xp, ax = split_padded(parts, torch.randn(n, hh, ww, cin, device=dev), n, hh, ww, cin)
+    dyp, ady = split_padded(parts, torch.randn(n, hh, ww, cout, device=dev), n, hh, ww, cout)
+    dw = torch.full((cout * 9 * cin,), 7.0, device=dev)
+    ops.conv3x3_wgrad_split(parts, xp, dyp, dw, n, hh, ww, cin, cout, oscale=oscale(parts, ady, ax))
+    print("split", parts, "wgrad", n, hh, ww, cin, cout, *h(dw), float(dw.abs().max()))
+    # linear5's three contractions at the smallest shape goalnet_linear_split_ok admits
+    M, K, J = 256, 65536, 256
+    assert ops.linear_split_ok(parts, M, K, J)
+    xs, ax = split_rows(parts, torch.randn(M, K, device=dev), M, K)
+    wsp, aw = split_rows(parts, torch.randn(J, K, device=dev) * 0.02, J, K)
+    dys, ady = split_rows(parts, torch.randn(M, J, device=dev), M, J)
+    y = torch.full((M, J), 7.0, device=dev)
+    ops.linear_fwd_split(parts, xs, wsp, torch.randn(J, device=dev), y, M, K, J, relu=True, oscale=oscale(parts, ax, aw))
+    dx = torch.full((M, K), 7.0, device=dev)
+    ops.linear_bwd_dx_split(parts, dys, wsp, dx, M, K, J, oscale=oscale(parts, ady, aw))
+    dw = torch.full((J, K), 7.0, device=dev)
+    ops.linear_bwd_dw_split(parts, dys, xs, dw, M, K, J, oscale=oscale(parts, ady, ax))
+    print("split", parts, "linear", M, K, J, *h(y, dx, dw), float(y.abs().max()), float(dx.abs().max()), float(dw.abs().max()))

@@ -303,6 +303,18 @@ NV12_PROTOTYPES = {
 }
 NV12_MIN_SHIFT, NV12_MAX_SHIFT = 8, 24        # GOALNET_NV12_MIN_SHIFT / _MAX_SHIFT
 
+# name -> (restype, [argtypes])   — one row per entry point declared in include/goalnet_storyboard.h, the eleventh public header (the
+# static summary: keyframes, thumbnails and a contact sheet): additions, the tables above stay as they are. The NV12
+# colour table is HOST memory, as in NV12_PROTOTYPES
+STORYBOARD_PROTOTYPES = {
+    "goalnet_storyboard_keyframes": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P, c_int, P, P]),
+    "goalnet_storyboard_render": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "goalnet_storyboard_render_nv12": (c_int, [P, c_int, c_int, c_int, c_int64, c_int64, c_int64, ctypes.POINTER(c_int32), P, c_int, c_int,
+                                               c_int, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+}
+STORYBOARD_MAX_CLIPS = 4096       # GOALNET_STORYBOARD_MAX_CLIPS
+STORYBOARD_MAX_DIM = 16384        # GOALNET_STORYBOARD_MAX_DIM
+
 _lib = None
 
 
@@ -322,7 +334,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*PROTOTYPES.items(), *LOSS_PROTOTYPES.items(), *EPOCH_PROTOTYPES.items(), *OPTIM_PROTOTYPES.items(),
                               *EMA_PROTOTYPES.items(), *ACCUM_PROTOTYPES.items(), *GROUPS_PROTOTYPES.items(), *MIX_PROTOTYPES.items(),
-                              *WAVE_PROTOTYPES.items(), *NV12_PROTOTYPES.items()):
+                              *WAVE_PROTOTYPES.items(), *NV12_PROTOTYPES.items(), *STORYBOARD_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,17 @@ namespace goalnet {
 static inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 static inline size_t offsets_bytes(int n_clips) { return align256((size_t)(n_clips + 1) * sizeof(int64_t)); }
 
+// The frames [a, b) of clip c, clamped like a Python slice (as clip_info_kernel); b <= a: none. The one slice rule of the clip gathers
+// and of the keyframe choice (storyboard.hip).
+__device__ __forceinline__ void clip_slice(const int32_t* __restrict__ cps, int c, int full_n, int& a, int& b) {
+    a = cps[2 * c];
+    b = cps[2 * c + 1];
+    if (a < 0) a = a + full_n < 0 ? 0 : a + full_n;
+    if (b < 0) b = b + full_n < 0 ? 0 : b + full_n;
+    a = a > full_n ? full_n : a;
+    b = b > full_n ? full_n : b;
+}
+
 // One block. offsets[c] = number of summary frames in front of clip c (exclusive scan of the selected clips' slice lengths),
 // offsets[n_clips] = their total; starts[c] = first source frame of clip c. [a:b) clamped like a Python slice (as clip_info_kernel).
 static __global__ __launch_bounds__(256) void clip_offsets_kernel(const int32_t* __restrict__ cps, const int32_t* __restrict__ selected, int n_clips,
@@ -18,12 +29,8 @@ static __global__ __launch_bounds__(256) void clip_offsets_kernel(const int32_t*
     const int per = (n_clips + 255) / 256;
     const int lo = t * per < n_clips ? t * per : n_clips, hi = lo + per < n_clips ? lo + per : n_clips;
     auto slice = [&](int c, int& a) -> int {
-        a = cps[2 * c];
-        int b = cps[2 * c + 1];
-        if (a < 0) a = a + full_n < 0 ? 0 : a + full_n;
-        if (b < 0) b = b + full_n < 0 ? 0 : b + full_n;
-        a = a > full_n ? full_n : a;
-        b = b > full_n ? full_n : b;
+        int b;
+        clip_slice(cps, c, full_n, a, b);
         return (selected[c] != 0 && b > a) ? b - a : 0;
     };
     int64_t local = 0;

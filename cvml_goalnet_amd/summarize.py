@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import nv12
+from . import storyboard as _storyboard
 from .postprocess import SummaryEvaluator
 from .preprocess import SR, extract_audio_features, frames_to_tensor
 from .waveform import load_audio, to_mono
@@ -37,6 +38,7 @@ class VideoSummary:
     src_index: torch.Tensor        # (count,) int32 on the device: the source frame of every summary frame
     predictions: torch.Tensor      # (N, 1) float32 on the device: the model's importance of every sampled frame
     change_points: Optional[np.ndarray] = None   # (n_clips, 2) int32: the change points the summary was made with
+    storyboard: Optional[_storyboard.Storyboard] = None   # the static summary, when the call asked for one (cvml_goalnet_amd/storyboard.py)
 
 
 class VideoSummarizer:
@@ -84,7 +86,7 @@ class VideoSummarizer:
 
     def __call__(self, full_frames, audio_features=None, waveform=None, sr: int = SR, bin_length=None, audio_fp=None,
                  target_sr=None, pixel_format: str = "bgr", frame_size=None, uv_row=None, colorspace="bt601",
-                 output_format: str = "bgr") -> VideoSummary:
+                 output_format: str = "bgr", storyboard=None) -> VideoSummary:
         """full_frames: (full_n, H0, W0, 3) uint8, the decoded video (`get_frame_tensor`, utils.py:294-305), on the GPU or the host.
         With `audio_included=True` give either audio_features (N, 30, B) for the N = ceil(full_n / skip_frames) sampled frames, or
         the decoded `waveform` at `sr` together with `bin_length` (the reference's own call at main.py:321 omits bin_length and
@@ -97,7 +99,13 @@ class VideoSummarizer:
         (H0, W0), the chroma plane at row `uv_row` (default H0) and the colour table `colorspace` (cvml_goalnet_amd/nv12.py). The
         sampled frames are converted inside the pre-processing and the selected clips inside the gather; no BGR copy of the video
         is made. output_format="bgr" (the default) returns `frames` as (count, H0, W0, 3), what `export_video` takes;
-        output_format="nv12" returns the selected source frames as they are, (count, rows, pitch), for a hardware encoder."""
+        output_format="nv12" returns the selected source frames as they are, (count, rows, pitch), for a hardware encoder.
+        storyboard: None, or a dict of `size` (tw, th), `cols`, `gap`, `background`, `max_keyframes`, `clips` ("selected", the
+        default, or "all"): the result then carries `VideoSummary.storyboard` (cvml_goalnet_amd/storyboard.py), one
+        keyframe per selected clip (or per clip) with its thumbnail, and with `cols` the contact sheet. It is made from this call's own
+        predictions, change points, flags and source video, BGR or NV12, behind the read-back the summary already does and with none
+        of its own. Without the option nothing is launched and the result is what it was."""
+        board = None if storyboard is None else _storyboard.check_options(storyboard)
         model = self.model
         t = full_frames if torch.is_tensor(full_frames) else torch.from_numpy(np.ascontiguousarray(full_frames))
         if pixel_format not in nv12.PIXEL_FORMATS:
@@ -157,4 +165,7 @@ class VideoSummarizer:
                 cps = self.change_points
                 ev = self._evaluator(full_n)
             frames, mask = ev.summarize(predictions, t) if layout is None else ev.summarize(predictions, t, nv12_layout=layout)
-        return VideoSummary(frames, mask, ev.last_selected, ev.last_src_index, predictions, cps)
+            if board is not None:
+                board = _storyboard.from_summary(board, predictions, cps, ev.cps, ev.selected, ev.last_selected, self.skip_frames, t,
+                                                 None if layout is None else layout[:3])
+        return VideoSummary(frames, mask, ev.last_selected, ev.last_src_index, predictions, cps, board)
